@@ -14,8 +14,14 @@ MaxRestart 3, SYMMETRY symmServers, VIEW view, INVARIANT Inv, -deadlock -- 10,94
 states, depth 72, on one GPU in ~13 s.  `value` = its distinct states / the time of one
 exhaustion, `ms_per_step` = that time.  The `roofline` block is its dominant kernel, the split
 chunks' item-parallel expansion (k_expand_items<..., false, 64>), timed with HIP events on the
-engine's stream.  BASELINE configs[1] (3 servers, 1 value, MaxElection 2: 223,437 states in ~1.8 ms)
-is reported under the `configs1` key (N = 1).
+engine's stream.
+
+A plain run sets up, warms up, times the --steps exhaustions, writes the last one's results if
+--dump-outputs DIR is given (dump_outputs) and prints the line; everything in it comes from the timed
+steps themselves.  --full adds what takes runs of its own: the seen-set's random-probe peaks
+(`seen_set`, `survey_roofline`'s roofline time), BASELINE configs[1] (3 servers, 1 value, MaxElection 2:
+223,437 states in ~1.8 ms) under the `configs1` key (N = 1), the CPU restatement's rate (`cpu_baseline`)
+and the comparison of the levels with the C oracle's prefix (`config.matches_c_oracle_prefix_levels`).
 
 N > 1 (torchrun, one process per GPU): the same Raft.cfg exhaustion by all ranks together through
 the engine's multi-GPU mode: levels below rmc_config.shard_min_states (2^20)
@@ -613,15 +619,46 @@ def record_bytes(res, cfg):
     return (nb / ns if ns else float(ccwb)), ccwb
 
 
+LEVEL_OUTPUTS = ("expanded", "generated", "new_states", "total_generated", "total_distinct", "queue", "new_bytes",
+                 "self_loops")
+
+
+def dump_outputs(res, outdir):
+    """--dump-outputs: what the last timed exhaustion returned to its caller (raftmc.Result, timings left
+    out), one float64 array per file (every count is below 2^53, so the values are exact): result.npy =
+    [status code, depth, states generated, distinct states, queue, trace length] and, per level of the
+    breadth-first search, level_<field>.npy for each field of LEVEL_OUTPUTS plus level_status.npy.  The
+    workload has no input data (the state space is generated from Init), so two runs with the same
+    arguments must write the same arrays."""
+    import numpy as np
+    import raftmc
+    code = {name: c for c, name in raftmc.STATUS_NAMES.items()}
+    os.makedirs(outdir, exist_ok=True)
+
+    def save(name, values):
+        np.save(os.path.join(outdir, name + ".npy"), np.array(values, dtype=np.float64))
+
+    levels = list(res.levels)
+    save("result", [code[res.status], res.depth, res.generated, res.distinct, res.queue, res.trace_len])
+    save("level_status", [code[ls.status] for ls in levels])
+    for name in LEVEL_OUTPUTS:
+        save("level_" + name, [getattr(ls, name) for ls in levels])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="raftcfg", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe-peak", action="store_true")
-    ap.add_argument("--no-configs1", action="store_true", help="skip the configs[1] leg (N = 1)")
+    ap.add_argument("--full", action="store_true", help="after the headline's timed steps also run what takes runs "
+                    "of its own: the seen-set probe peaks, the configs[1] leg, the CPU baselines and the "
+                    "comparison with the C oracle's prefix levels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned as "
+                    "DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-probe-peak", action="store_true", help="--full without the probe peaks")
+    ap.add_argument("--no-configs1", action="store_true", help="--full without the configs[1] leg (N = 1)")
     ap.add_argument("--chunk-successors", type=int, default=0,
                     help="successor slots per chunk (0: the engine's default; a tuning run)")
     ap.add_argument("--configs3", action="store_true", help="N > 1: first take configs[3] as deep as the node's "
@@ -630,6 +667,8 @@ def main():
     ap.add_argument("--sharded-out", default="", help=argparse.SUPPRESS)
     ap.add_argument("--child-budget", type=float, default=C4_BUDGET_S, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.sharded_child:
         sharded_child(args)
         return
@@ -695,23 +734,26 @@ def main():
         roof["counters_at_scale"] = counters_at_scale(args.workload) if args.workload == "raftcfg" else None
     else:
         roof = phase_roofline(timed, S, mc.cfg, args.workload, res.depth)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(res, args.dump_outputs)
     self_loops = sum(ls.self_loops for ls in res.levels)
-    match, prefix_levels = oracle_prefix_match(res, w)
     config = {"workload": w["desc"], "distinct_states": res.distinct, "states_generated": res.generated,
               "depth": res.depth, "verdict": "Inv holds" if res.status == "done" else res.status,
               "parallelism": parallelism, "self_loops": self_loops,
               "self_loop_frac": round(self_loops / max(1, res.generated), 4),
               "seen_set": f"{res.seen_slots} x {res.seen_slot_bytes} B slots (rank 0)",
               "frontier_ring_bytes": res.frontier_ring_bytes, "frontier_peak_bytes": res.frontier_peak_bytes,
-              "first_run_seconds_incl_allocation": round(first_s, 3) if first_s else None,
-              "matches_c_oracle_prefix_levels": match, "c_oracle_prefix_levels": prefix_levels}
+              "first_run_seconds_incl_allocation": round(first_s, 3) if first_s else None}
+    if args.full:
+        match, prefix_levels = oracle_prefix_match(res, w)
+        config.update({"matches_c_oracle_prefix_levels": match, "c_oracle_prefix_levels": prefix_levels})
     # seen-set probe throughput of the run (one probe per fingerprinted successor, one insert per new state)
     # against the random-probe peak of the slot layout measured on this GPU: a table far beyond the caches
     # (2^28 16-B slots = 4 GiB, HBM-resident) and one of 2^22 slots (L2/MALL-resident)
     probes = res.generated - self_loops + res.distinct
     seen = {"probes_per_step": probes, "achieved_probes_per_s": round(probes * args.steps / elapsed, 1)}
     pk_hbm = None
-    if rank == 0 and not args.no_probe_peak:
+    if args.full and rank == 0 and not args.no_probe_peak:
         pk_small = raftmc.probe_peak(local, 22, 1 << 26)
         pk_hbm = raftmc.probe_peak(local, 28, 1 << 28)
         seen.update({"peak_probes_per_s_2^22_slots": round(pk_small, 1),
@@ -739,9 +781,9 @@ def main():
         line["xgmi_bytes_model"] = xgmi_model(res.levels, rworld)
         line["xgmi_GBps_avg"] = round(line["xgmi_bytes_model"] / (elapsed / args.steps) / 1e9, 2)
     mc.close()
-    if rank == 0 and world == 1 and args.workload != "c2" and not args.no_configs1:
+    if args.full and rank == 0 and world == 1 and args.workload != "c2" and not args.no_configs1:
         line["configs1"] = configs1_leg(local, args, pk_hbm)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = (cpu_baseline_raftcfg(local) if args.workload == "raftcfg" else
                                 cpu_baseline(w) if args.workload == "c2" else None)
     if rank == 0 and sharded_c4 is not None:

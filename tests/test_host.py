@@ -341,6 +341,28 @@ def test_bench_counters_at_scale_read_from_profiles():
         assert c[k]["ratio"] == v["aggregate"]["ratio"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the run's status and totals and every per-level count of the last timed step's
+    result, as exact float64 arrays (Raft.cfg's totals are past 2^32), timings left out."""
+    import numpy as np
+    from types import SimpleNamespace as L
+    bench = _bench()
+
+    def lv(k, status="ok"):
+        return L(status=status, seconds=0.5 * k, **{name: 10 * k + i for i, name in enumerate(bench.LEVEL_OUTPUTS)})
+    res = L(status="done", depth=72, generated=56936653204, distinct=10946499503, queue=0, trace_len=0, seconds=11.6,
+            levels=[lv(1), lv(2), lv(3, "done")])
+    out = tmp_path / "dump"
+    bench.dump_outputs(res, str(out))
+    got = {p.name[:-4]: np.load(p) for p in out.iterdir()}
+    assert set(got) == {"result", "level_status"} | {"level_" + name for name in bench.LEVEL_OUTPUTS}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["result"].tolist() == [raftmc.RMC_DONE, 72, 56936653204, 10946499503, 0, 0]
+    assert got["level_status"].tolist() == [raftmc.RMC_OK, raftmc.RMC_OK, raftmc.RMC_DONE]
+    for i, name in enumerate(bench.LEVEL_OUTPUTS):
+        assert got["level_" + name].tolist() == [10 + i, 20 + i, 30 + i]
+
+
 def test_error_variant_specs_recognised():
     """tools/make_seeded_spec.py --split-brain / --commit-past-log on Raft.tla (skipped where the
     reference is absent): the parser maps each text to its variant by content hash."""

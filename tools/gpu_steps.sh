@@ -4,7 +4,7 @@
 #   tests        pytest -m gpu (whole suite)        tests:K  pytest -m gpu -k K
 #   raftcfg      Raft.cfg exhausted level by level (tools/explore.py)
 #   prof_raftcfg rocprofv3 kernel stats of the same
-#   bench        bench.py default line (Raft.cfg, 10 steps)   benchd  the driver's line (--steps 20 --warmup 5)
+#   bench        bench.py --full line (Raft.cfg, 10 steps)   benchd  the same with --steps 20 --warmup 5
 #   prof_bench   rocprofv3 kernel stats of bench's headline (Raft.cfg, 2 timed steps)
 #   prof_c2      rocprofv3 kernel stats of bench --workload c2 (configs[1])
 #   pmc_bench    tools/pmc.sh over bench's headline (one Raft.cfg exhaustion per pass) + pmc_summary.py
@@ -34,9 +34,9 @@ for s in "$@"; do
            tail -4 "$O/raftcfg.log" ;;
     prof_raftcfg) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_raftcfg" -o run -- python3 "$R/tools/explore.py" 3 2 3 3 --budget 200 > "$O/prof_raftcfg.log" 2>&1 || { tail -20 "$O/prof_raftcfg.log"; exit 1; }
            grep RESULT "$O/prof_raftcfg.log"; find "$O/prof_raftcfg" -name '*kernel_stats.csv' -exec head -12 {} \; ;;
-    bench) timeout -k 10 600 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail "$O/bench.err"; exit 1; }
+    bench) timeout -k 10 600 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail "$O/bench.err"; exit 1; }
            cut -c1-600 "$O/bench.json" ;;
-    benchd) timeout -k 10 900 python -u bench.py --steps 20 --warmup 5 > "$O/benchd.json" 2> "$O/benchd.err" || { tail "$O/benchd.err"; exit 1; }
+    benchd) timeout -k 10 900 python -u bench.py --full --steps 20 --warmup 5 > "$O/benchd.json" 2> "$O/benchd.err" || { tail "$O/benchd.err"; exit 1; }
            cut -c1-600 "$O/benchd.json" ;;
     prof_bench) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_bench" -o bench -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-configs1 --no-cpu-baseline --no-probe-peak > "$O/prof_bench.log" 2>&1 || { tail -20 "$O/prof_bench.log"; exit 1; }
            tail -c 700 "$O/prof_bench.log"; find "$O/prof_bench" -name '*kernel_stats.csv' -exec head -12 {} \; ;;
