@@ -10,7 +10,8 @@
 //   * the reverse plan brings every verdict back to the slot it answers;
 //   * every winner lands on the shard (g / B) % W at the position the block-cyclic layout gives
 //     it, in global order, whether the source sends its pieces in place or regrouped;
-//   * must_grow names exactly the shards whose receive need reaches their capacity.
+//   * must_grow names exactly the shards whose receive need reaches their capacity;
+//   * chunk_slots_fit_u32 accepts a chunk exactly when its parents x maxsucc stays below 2^32.
 // Exit status 0 and "plan ok" on success.
 #include <cstdio>
 #include <cstdlib>
@@ -203,6 +204,22 @@ int main() {
             }
         }
     }
+    // ---- 32-bit slot bases: a chunk fits iff parents x maxsucc < 2^32 (exact at the boundary, no
+    // overflow of the product; 288 / 301: the BecomeFollower variant at 4 / 5 servers) ----
+    for (uint64_t ms : {1ull, 72ull, 173ull, 256ull, 288ull, 301ull, 1024ull, 65536ull, 0xFFFFFFFFull, 1ull << 32}) {
+        const uint64_t most = ((1ull << 32) - 1) / ms;  // the largest parent count that fits
+        CHECK(chunk_slots_fit_u32(0, ms));
+        CHECK(chunk_slots_fit_u32(1, ms) == (ms < (1ull << 32)));
+        CHECK(most == 0 || chunk_slots_fit_u32(most, ms));
+        CHECK(most * ms < (1ull << 32) && (most + 1) * ms >= (1ull << 32));
+        CHECK(!chunk_slots_fit_u32(most + 1, ms));
+        if (ms > 1) CHECK(!chunk_slots_fit_u32(~0ull / ms + 1, ms));  // the product wraps 2^64
+        CHECK(!chunk_slots_fit_u32(~0ull, ms));
+    }
+    CHECK(!chunk_slots_fit_u32(1, 0));                                   // no kernel set
+    CHECK(chunk_slots_fit_u32((1ull << 30) / 288, 288));                 // the engine's largest chunk_successors
+    CHECK(chunk_slots_fit_u32((uint64_t)1024 * 4096, 1023));             // the winner-count tiles' bound, widest rank
+    CHECK(!chunk_slots_fit_u32((uint64_t)1024 * 4096, 1024));            // ... exactly 2^32
     if (fails) {
         std::printf("%d failures\n", fails);
         return 1;

@@ -111,6 +111,21 @@ def test_ranks_identical_to_single(name, W, shard_min, tmp_path):
             assert r["trace"] == exp
 
 
+def test_ranks_split_rounds_above_256_slots(tmp_path, monkeypatch):
+    """Two rank processes, every round split (RMC_SPLIT_MIN=1 reaches the ranks through run_ranks'
+    environment), the BecomeFollower variant at 4 servers: 288 successor slots per state, so each rank's
+    own candidates are decided by k_local_flags and committed by k_commit_split -- the golden levels and
+    counters on both ranks."""
+    monkeypatch.setenv("RMC_SPLIT_MIN", "1")
+    g = LEVELS["bf_n4_v1_e1_r3"]
+    rs = run_ranks(tmp_path, 2, golden_cfg(g, chunk_successors=3000, shard_min_states=1))
+    errs = [r.get("error") for r in rs]
+    assert not any(errs), "\n".join(f"rank {i}: {e}\n{r['_log']}" for i, (e, r) in enumerate(zip(errs, rs)))
+    for r in rs:
+        check(g, r)
+        assert r["levels"] == rs[0]["levels"]
+
+
 @pytest.mark.parametrize("site", [1, 2, 3, 4, 6, 7])
 def test_ranks_agree_on_allocation_failure(site, tmp_path):
     """The allocation at `site` fails on rank 1 only, in round 1 of level 14 of configs[1]: both

@@ -4,7 +4,9 @@ The engine's RCCL branch and its virtual-shard branch derive every offset of the
 all-to-all-v payloads from rmc_plan.h; tests/plan_test.cpp simulates those payloads at W = 1..8 on
 host arrays and checks that the RCCL ranks' posted sends/receives equal the virtual copies, that
 verdicts come back to their slots, that winners land on their block-cyclic owners in global order,
-and that receive growth is decided identically on every rank (no W > 1 path can run here)."""
+and that receive growth is decided identically on every rank (no W > 1 path can run here); and that
+chunk_slots_fit_u32, by which the engine refuses a chunk whose parents x maxsucc would reach 2^32 (the
+kernels' 32-bit slot bases), is exact at the boundary."""
 import os
 import shutil
 import subprocess

@@ -986,6 +986,9 @@ struct rmc_ctx {
         chunk_parents = Gcap / ks.maxsucc;
         shard_min = multi ? (cfg.shard_min_states ? cfg.shard_min_states : (1ull << 20)) : 0;
         chunk_parents = std::min<uint64_t>(chunk_parents, (uint64_t)WTILE * WTILES_MAX);  // winner-count tiles
+        // (32-bit slot bases in the kernels: k_commit_items' sHo, hoff, each_successor's h0)
+        if (!chunk_slots_fit_u32(chunk_parents, (uint64_t)ks.maxsucc))
+            throw Fail(RMC_E_CAPACITY, "a chunk's successor slots (chunk parents x slots per state) must be < 2^32");
         Lcap_max = next_pow2(2 * Gcap);
 
         sh.resize(virt ? W : 1);
@@ -2577,6 +2580,10 @@ struct rmc_ctx {
     // global next-level indices, appended in source order -- the level's order.  Levels, counters
     // at an error and traces are those of W = 1.
     bool round_sep(const Shard &s) const { return split_min && s.np >= split_min; }
+    // ... and its commit decides the shard's own candidates only where commit_split (rmc_kernels.hip
+    // Launch) selects k_commit_items, i.e. a parent's slots fit its 256 lanes (step_single's `fold`);
+    // k_commit_split (the BecomeFollower variant at n >= 4: 288 / 301 slots) takes LS_WIN verdicts only
+    bool round_commit_decides(const Shard &s) const { return round_sep(s) && ks.maxsucc <= 256; }
     KParams round_params(const Shard &s, uint64_t gbase) const {
         KParams Q = chunk_params(s);
         Q.p_begin = s.p0;
@@ -2833,8 +2840,14 @@ struct rmc_ctx {
                         OT = o.OT;
                         rnd = o.ot_round;
                     }
-                    // every bid counts the owner's own winners on their parents (owner_bid); a split round's commit
-                    // then decides the own candidates itself (no k_local_flags pass)
+                    // every bid counts the owner's own winners on their parents (owner_bid) -- those k_hash_probe made
+                    // in E and those redone in the owner table alike -- so wacc is exact whoever decides them after.
+                    // A split round whose commit is k_commit_items (round_commit_decides: commit_split selects it at
+                    // maxsucc <= 256) decides the own candidates there, inserts the winners and counts them in
+                    // SUM_INS_COMMIT: no k_local_flags pass.  Every other round -- below the split size, or a split
+                    // round that commit_split hands to k_commit_split (maxsucc > 256), which reads LS_WIN verdicts
+                    // only -- decides them in k_local_flags: verdicts in lslot, inserts counted in SUM_INS, and
+                    // SUM_INS_COMMIT stays at the 0 the round's memset left
                     timed(PH_DEDUP, [&] {
                         const KParams Q = round_params(o, gbase);
                         if (Rl && !lx) {
@@ -2847,7 +2860,7 @@ struct rmc_ctx {
                             launch_owner_elect(o.xr, R, o.seen(), OT, mask, rnd, o.rslot, o.wacc, o.gblk, o.np, stream);
                             launch_owner_flags(o.xr, R, o.rslot, OT, rnd, o.seen(), o.rflag, o.sum + SUM_INS, stream);
                         }
-                        if (Rl && !round_sep(o))
+                        if (Rl && !round_commit_decides(o))
                             ks.local_flags(Q, o.np, o.seen(), OT, rnd, (uint32_t)W, (uint32_t)o.id, o.gblk,
                                            o.sum + SUM_INS, stream);
                     });
@@ -2897,6 +2910,7 @@ struct rmc_ctx {
                     timed(PH_MAT, [&] {
                         KParams Q = round_params(s, gbase);
                         if (Q.plist) {  // a lane per successor slot; the own candidates decided in the round's table
+                                        // (by k_commit_items; k_local_flags has left verdicts where k_commit_split runs)
                             Q.OT = s.rt_table;
                             Q.ot_round = s.rt_round;
                             ks.commit_split(Q, s.np, stream);

@@ -3712,9 +3712,10 @@ __global__ __launch_bounds__(256) void k_local_elect(KParams P, Seen seen, ESlot
     });
 }
 
-// ... once every bid of the round is in (the received ones too), a round below the split size (a split
-// round's commit decides its own candidates itself): the verdict in lslot (LS_WIN / LS_SEEN) and each
-// winner into the seen set, *inserted counting them (the bids counted the winners on their parents).
+// ... once every bid of the round is in (the received ones too), a round below the split size or one
+// whose commit is k_commit_split (MX > XB_THREADS; a split round that k_commit_items commits decides its
+// own candidates there): the verdict in lslot (LS_WIN / LS_SEEN) and each winner into the seen set,
+// *inserted counting them (the bids counted the winners on their parents).
 template <int MX>
 __global__ __launch_bounds__(256) void k_local_flags(KParams P, Seen seen, const ESlot *OT, uint32_t round,
                                                      uint32_t W, uint32_t self, uint64_t g0,

@@ -121,6 +121,13 @@ inline PieceLayout piece_layout(const std::vector<Piece> &pcs, int W) {
     return L;
 }
 
+// The kernels keep a chunk's successor-slot bases in 32 bits (a parent's first slot, chunk parent x
+// maxsucc or its dense offset): a chunk of `parents` parents fits only if parents x maxsucc < 2^32.
+// The engine refuses (RMC_E_CAPACITY) a chunk size for which this is false, where it sizes the chunk.
+inline bool chunk_slots_fit_u32(uint64_t parents, uint64_t maxsucc) {
+    return maxsucc != 0 && parents <= 0xFFFFFFFFull / maxsucc;
+}
+
 // Shards whose receive buffer must grow before the payload moves: need[r] + 1 > cap[r].  Every rank
 // computes the same list from the gathered matrix, so all of them take the extra agreement step.
 inline std::vector<int> must_grow(const std::vector<uint64_t> &need, const std::vector<uint64_t> &cap) {
