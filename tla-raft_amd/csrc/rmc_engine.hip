@@ -616,6 +616,24 @@ struct rmc_ctx {
     const int lookahead = env_int("RMC_LOOKAHEAD", 1, 0, 1);
     bool two_sets() const { return lookahead && !multi; }
 
+    // ---- k_hash_probe's table of recent fingerprints (single-GPU split chunks) ---------------------
+    // RMC_PROBE_DEDUP (read once): 0 = every successor is probed; unset or 1 = each wave keeps a table
+    // of PD_ENTRIES fingerprints and drops the repeats of an earlier successor of its own before the
+    // seen-set probe; a power of two from 2 up = that many entries (tests: evictions and entry
+    // conflicts on small inputs).  RMC_PROBE_RUN: the groups of 64 parents a wave takes in a row
+    // (unset or 0: up to PROBE_RUN, fewer on a small chunk -- Launch::hash_probe).
+    // RMC_PROBE_DEDUP_LOG=1: a line per level on stderr with the successors dropped.
+    static uint32_t probe_dedup_entries() {
+        const int v = env_int("RMC_PROBE_DEDUP", 1, 0, (int)PD_ENTRIES);
+        if (v <= 1) return v ? PD_ENTRIES : 0u;
+        uint32_t n = 2;
+        while (2 * n <= (uint32_t)v) n *= 2;
+        return n;
+    }
+    const uint32_t probe_dedup = probe_dedup_entries();
+    const uint32_t probe_run = (uint32_t)env_int("RMC_PROBE_RUN", 0, 0, 64);
+    const int probe_log = env_int("RMC_PROBE_DEDUP_LOG", 0, 0, 1);
+
     // the other set becomes the one the Shard's members (and so base / chunk_params, error_counts)
     // name, with the events of the expansion that filled it
     void swap_staging(Shard &s) {
@@ -2038,7 +2056,7 @@ struct rmc_ctx {
         st->expanded = s.cur_n;
         const uint64_t gid_cur = s.level_start[L - 1];
         const uint64_t gid_nxt = gid_cur + s.cur_n;
-        uint64_t level_gen = 0, level_self = 0;
+        uint64_t level_gen = 0, level_self = 0, level_hfp = 0, level_drop = 0;
         s.nxt_n = 0;
         s.nxt_words = 0;
         const uint64_t MSW = (uint64_t)ks.maxsucc * (uint64_t)ks.RECW_MAX;
@@ -2110,6 +2128,8 @@ struct rmc_ctx {
                 // (the dense slot layout: chunks whose winners the items commit takes -- k_insert_winners and
                 // k_commit_split read the sparse one)
                 Q.hoff = fold ? s.hoff : nullptr;
+                Q.pdedup = split ? probe_dedup : 0u;
+                Q.prun = probe_run;
                 s.chunk_sep = Q.hcnt != nullptr;
                 s.chunk_dense = Q.hoff != nullptr;
                 return Q;
@@ -2192,12 +2212,16 @@ struct rmc_ctx {
                 if (split) ks.commit_split(params(), np_, stream);
                 else ks.commit(params(), stream);
             });
-            HIPCHK(hipMemcpyAsync(s.hsum, s.sum, (SUM_SELF + 1) * 8, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(s.hsum, s.sum, (SUM_PDROP + 1) * 8, hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
             HIPCHK(hipGetLastError());
             collect_times(st);
             const uint64_t G = s.hsum[0], Wn = s.hsum[1], Ww = s.hsum[SUM_WORDS];
             level_self += s.hsum[SUM_SELF];
+            if (split) {
+                level_hfp += s.hsum[SUM_HFP];
+                level_drop += s.hsum[SUM_PDROP];
+            }
             if (s.hsum[2 + ERR_NSLOTS]) throw Fail(flag_code(s.hsum[2 + ERR_NSLOTS]), flag_msg(s.hsum[2 + ERR_NSLOTS]));
             flush_trace(s, gid_nxt + s.nxt_n + Wn);
             level_gen += G;
@@ -2220,6 +2244,9 @@ struct rmc_ctx {
         total_distinct += s.nxt_n;
         st->generated = level_gen;
         st->self_loops = level_self;
+        if (probe_log)
+            std::fprintf(stderr, "rmc probe_dedup: level %d fingerprinted %llu dropped %llu\n", L,
+                         (unsigned long long)level_hfp, (unsigned long long)level_drop);
         st->new_states = s.nxt_n;
         st->new_bytes = s.nxt_words * 4;
         end_level(s, gid_nxt, L);

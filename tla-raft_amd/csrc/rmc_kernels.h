@@ -86,8 +86,14 @@ constexpr int SUM_SELF = 17;     // ... and the self-loops set apart (KParams::h
                                  // zeroed by the host per chunk)
 constexpr int SUM_HFP = 18;      // ... and a split chunk's successors to fingerprint (its expansion counts them; the
                                  // election of k_hash_probe takes a table of twice as many slots; zeroed with SUM_SELF)
-constexpr int SUM_OCNT = 20;     // ... a sharded round's successors per owner shard (u32[64] over sum[20 .. 52): zeroed
+constexpr uint32_t PD_ENTRIES = 512;  // k_hash_probe: entries of 16 B in a wave's table of recent fingerprints
+constexpr int PROBE_RUN = 2;     // ... and the groups of 64 parents a wave takes in a row (KParams::prun)
+constexpr int SUM_OCNT = 20;    // ... a sharded round's successors per owner shard (u32[64] over sum[20 .. 52): zeroed
                                  // with SUM_INS .. SUM_HFP by one memset per round)
+constexpr int SUM_PDROP = 56;    // ... and a split chunk's successors that k_hash_probe dropped before the seen-set probe:
+                                 // repeats of an earlier successor of their wave (KParams::pdedup; zeroed with SUM_SELF).
+                                 // Not on the 128-B line of sum[SUM_HFP], which every block of k_hash_probe reads as it
+                                 // starts: one atomic per finished block would queue those reads behind it
 // the fused expansion's self-loop counters: SELF_STRIPES words a 128-B line apart (block b adds to stripe
 // b % SELF_STRIPES), folded by finish_level (k_set_ctl zeroes them for the device loop; 0 between levels)
 constexpr int SUM_SELF_STRIPE = 64, SELF_STRIDE = 16, SELF_STRIPES = 8;  // sum[64 .. 176]
@@ -161,6 +167,11 @@ struct KParams {
     // its verdicts in lslot (LS_WIN / LS_SEEN) for the commit
     int split;
     uint32_t *hctx;
+    // k_hash_probe of a single-GPU split chunk: entries in use of each wave's table of recent fingerprints
+    // (a power of two <= PD_ENTRIES; 0 = no table, every successor is probed), and the groups of 64
+    // parents a wave takes in a row, over which its table carries on (0: the launcher's choice, which it
+    // passes to the kernel here)
+    uint32_t pdedup, prun;
     // test variants: bit 0 RaftSplitBrain (BecomeLeader's quorum 1), bit 1 RaftCommitPastLog
     // (FollowerAcceptEntry's newCommitIndex without Min(., Len(newLog)))
     uint32_t quirks;

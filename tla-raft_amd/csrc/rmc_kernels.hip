@@ -1252,6 +1252,10 @@ __device__ __forceinline__ void seen_insert(const Seen &S, ulonglong2 f) {
 __device__ __forceinline__ uint64_t l_index(const ulonglong2 f, uint64_t mask) {
     return (f.x ^ (f.x >> 31) ^ (f.y >> 7)) & mask;
 }
+// k_hash_probe's table of recent fingerprints: bits that neither index above leans on alone
+__device__ __forceinline__ uint32_t pd_index(const ulonglong2 f) {
+    return (uint32_t)(f.x >> 17) ^ (uint32_t)(f.y >> 43);
+}
 // sharded run: owner(fp) = high bits of fp.y mod W -- independent of the seen-set and election index bits
 __device__ __forceinline__ uint32_t fp_owner(const ulonglong2 f, uint32_t W) {
     return (uint32_t)((f.y >> 40) % W);
@@ -2501,13 +2505,19 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
 // successor counts are scanned across the wave and successor i of the group goes to lane i % 64 of
 // round i / 64 (its parent found by a binary search over the scan); f(parent pl, rank r, its slot sq):
 // sq = pl * MX + r in the sparse layout, P.hoff[pl] + r in a dense split chunk's.
+// run: the groups a wave takes in a row (ascending) before it strides on -- a wave visits its
+// successors in increasing TLC order q = pl * MX + r whatever the run (k_hash_probe's table of recent
+// fingerprints rests on that).
 template <int MX, class F>
-__device__ __forceinline__ void each_successor(const KParams &P, F &&f) {
+__device__ __forceinline__ void each_successor(const KParams &P, F &&f, uint32_t run = 1) {
     const int lane = threadIdx.x & 63;
     const uint64_t np = P.p_end - P.p_begin;
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t g0 = ((uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 64; g0 < np;
-         g0 += nwaves * 64) {
+    const uint64_t span = (uint64_t)run * 64;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (wave-uniform: the loops stay scalar)
+    for (uint64_t r0 = ((uint64_t)blockIdx.x * (blockDim.x >> 6) + wv) * span; r0 < np;
+         r0 += nwaves * span)
+    for (uint64_t g0 = r0; g0 < r0 + span && g0 < np; g0 += 64) {
         const uint64_t pl = g0 + (uint64_t)lane;
         const uint32_t t = pl < np ? (P.hcnt ? P.hcnt : P.cnt)[pl] : 0u;  // (a split chunk: its self-loops are not visited)
         const uint32_t h0 = (pl < np && P.hoff) ? P.hoff[pl] : 0u;
@@ -2629,6 +2639,22 @@ __global__ __launch_bounds__(256, RMC_PROBE_WAVES) void k_hash_probe(KParams P) 
         sK[f][a * N + b] = P.t.seeds[f * SEEDS_PER_F + a * MAXN + b];
     }
     if (threadIdx.x < 64) sOwn[threadIdx.x] = 0u;
+    // Single-GPU split chunk: each wave's table of the fingerprints it met last (direct-mapped, P.pdedup
+    // entries in use, empty = x 0: a fingerprint's x is odd).  A successor whose whole fingerprint {x, y}
+    // an earlier successor of the wave has can never win -- new, the earlier one (smaller q: a wave walks
+    // its groups and rounds in increasing q, each_successor) outbids it; seen, both lose -- so its verdict
+    // LS_SEEN is known before the two random lines of probe_elect.  A table belongs to one wave (two
+    // waves' progress is not ordered by q) and is cleared only here.
+    __shared__ ulonglong2 sTab[4 * PD_ENTRIES];
+    __shared__ uint32_t sDrop;
+    const int lane = threadIdx.x & 63;
+    const uint32_t pdN = P.route ? 0u : P.pdedup;
+    const uint32_t tab0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * PD_ENTRIES;
+    uint32_t ndrop = 0;  // the wave's dropped successors (wave-uniform)
+    if (pdN) {
+        for (uint32_t k = (uint32_t)lane; k < pdN; k += 64) sTab[tab0 + k] = make_ulonglong2(0ull, 0ull);
+        if (threadIdx.x == 0) sDrop = 0u;
+    }
     // The election table of the chunk: twice its successors to fingerprint (counted by the expansion), not
     // the host's bound of MAXS per parent -- ~35x fewer slots at Raft.cfg's depth, so the elections' random
     // lines stay in the caches far more often (every slot of the table is free for this chunk's tag, so any
@@ -2679,9 +2705,51 @@ __global__ __launch_bounds__(256, RMC_PROBE_WAVES) void k_hash_probe(KParams P) 
             }
             return;
         }
+        if (pdN) {
+            // Entries are written whole, by one lane per entry and round: the lanes that miss claim the entry
+            // with a CAS from the x they all just read to a word no fingerprint has (even, not 0: the
+            // claimer's (q + 1) << 1), so exactly one succeeds; it stores its fingerprint, and only then do the
+            // others read the entry again.  Every LDS access of a wave completes in program order, and nobody
+            // waits for a lane of its own wave.  A lane is dropped only if both words equal its own and the
+            // writer was an earlier round's lane or a lane of this round with a smaller q (the CAS tells a
+            // loser who claimed).
+            unsigned long long *ex = &sTab[tab0 + (pd_index(f) & (pdN - 1u))].x, *ey = ex + 1;
+            const unsigned long long ox = __hip_atomic_load(ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            const unsigned long long oy = __hip_atomic_load(ey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            bool drop = ox == f.x && oy == f.y;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if (!drop) {
+                unsigned long long cur = ox;
+                const unsigned long long claim = (q + 1ull) << 1;
+                const bool won = __hip_atomic_compare_exchange_strong(ex, &cur, claim, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                                      __HIP_MEMORY_SCOPE_WAVEFRONT);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                if (won) {
+                    __hip_atomic_store(ey, f.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    __hip_atomic_store(ex, f.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (!won && !(cur & 1ull) && cur < claim) {  // claimed by a lane of smaller q
+                    const unsigned long long nx = __hip_atomic_load(ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    const unsigned long long ny = __hip_atomic_load(ey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    drop = nx == f.x && ny == f.y;
+                }
+            }
+            ndrop += (uint32_t)__popcll(__ballot(drop));
+            if (drop) {
+                P.lslot[sq] = LS_SEEN;
+                return;
+            }
+        }
         const uint32_t nm = (pc[Lo::W_MISC] >> 16) & 0xFFu;
         P.lslot[sq] = probe_elect<MX>(P, f, q, (nadd + (nm & 1u) + 1u) >> 1, Lmask);
-    });
+    }, P.prun);
+    if (pdN) {  // the chunk's dropped successors (sum[SUM_PDROP]; the host zeroes it with SUM_SELF)
+        if (lane == 0 && ndrop) atomicAdd(&sDrop, ndrop);
+        __syncthreads();
+        if (threadIdx.x == 0 && sDrop) atomicAdd(&P.sum[SUM_PDROP], (unsigned long long)sDrop);
+    }
     if (P.route && P.ocnt) {
         __syncthreads();
         if (threadIdx.x < P.nown && sOwn[threadIdx.x]) atomicAdd(&P.ocnt[threadIdx.x], sOwn[threadIdx.x]);
@@ -3764,9 +3832,15 @@ struct Launch {
                            dim3(items_threads<N, V, MR, false>()), 0, s, P);
     }
     static void hash_probe(const KParams &P, uint64_t np, hipStream_t s) {
-        const uint64_t blocks = (np + 255) / 256;  // four one-group waves per block
+        // four waves per block, a run of groups each: one group in a sharded round; else P.prun if set, or up to
+        // PROBE_RUN as long as the grid keeps 1024 blocks (four per CU: every CU busy on a small chunk)
+        KParams Q = P;
+        const uint64_t fit = np / (256ull * 1024ull);
+        Q.prun = P.route ? 1u : P.prun ? P.prun : (uint32_t)(fit < 1 ? 1 : fit < (uint64_t)PROBE_RUN ? fit : (uint64_t)PROBE_RUN);
+        const uint64_t per = 256ull * Q.prun;
+        const uint64_t blocks = (np + per - 1) / per;
         hipLaunchKernelGGL((k_hash_probe<N, V, MR, MX>), dim3(blocks ? (unsigned)(blocks < 16384ull ? blocks : 16384ull) : 1u),
-                           dim3(256), 0, s, P);
+                           dim3(256), 0, s, Q);
     }
     static void insert(const KParams &P, uint64_t np, hipStream_t s) {
         const uint64_t blocks = (np + 255) / 256;
