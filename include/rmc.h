@@ -72,17 +72,27 @@ extern "C" {
  * (Raft.cfg:33-34) and TLC's -deadlock flag (myrun.sh:3) bind.  VIEW view
  * (Raft.cfg:26) is always on; SYMMETRY symmServers (Raft.cfg:24) unless
  * no_symmetry.  A zero-initialised struct plus the four constants and
- * invariants = RMC_INV_LEADER_HAS_ALL_COMMITTED is Raft.cfg under myrun.sh. */
+ * invariants = RMC_INV_LEADER_HAS_ALL_COMMITTED is Raft.cfg under myrun.sh.
+ *
+ * Kernels are compiled for these (n_servers, n_vals, message lanes) only; rmc_create refuses
+ * every other combination with RMC_E_ARG ("no compiled kernels for ..."), before it touches the
+ * device:
+ *     64 lanes  (msg_cap 1..64):   (2,1) (2,2) (3,1) (3,2) (3,3)
+ *     128 lanes (msg_cap above 64): (3,1) (3,2) (4,1) (4,2) (5,1) (5,2)
+ * each with and without RMC_SPEC_BECOME_FOLLOWER.  So 4 and 5 servers need the 128 lanes (the
+ * default there) and take at most 2 values; 3 values exist only at 3 servers with 64 lanes. */
 typedef struct rmc_config {
-    int32_t n_servers;      /* |Servers|   Raft.cfg:18, 1..5 */
-    int32_t n_vals;         /* |Vals|      Raft.cfg:21, 0..3 */
+    int32_t n_servers;      /* |Servers|   Raft.cfg:18, 2..5 (see the table above) */
+    int32_t n_vals;         /* |Vals|      Raft.cfg:21, 1..2; 3 at 3 servers with 64 lanes */
     int32_t max_election;   /* MaxElection Raft.cfg:4,  0..7 */
     int32_t max_restart;    /* MaxRestart  Raft.cfg:3,  0..15 */
     uint32_t invariants;    /* RMC_INV_* bits (order: invariant_order) */
     int32_t check_deadlock; /* 0 = TLC -deadlock (myrun.sh:3) */
     int32_t spec_variant;   /* RMC_SPEC_* */
     int32_t device;         /* HIP device ordinal (-1 = current) */
-    int32_t msg_cap;        /* max |msgs| per state: 0 = auto (64 for n<=3, 128 otherwise) */
+    int32_t msg_cap;        /* max |msgs| per state: 0 = auto (64 for n<=3, 128 otherwise).  It selects the
+                               message lanes and is rounded up to them: 1..64 is 64 (msg_cap = 8 behaves as
+                               64), anything above 64 is 128; a state or successor past the lanes is RMC_E_CAPACITY */
     int32_t seen_log2;      /* initial seen-set slots = 2^seen_log2 (0 = auto); grows on demand */
     int32_t no_symmetry;    /* 0 = SYMMETRY symmServers (Raft.cfg:24); 1 = cfg without SYMMETRY */
     uint64_t chunk_successors; /* successors per device chunk (0 = auto) */

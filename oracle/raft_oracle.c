@@ -725,6 +725,15 @@ void orc_set_order(void *h, int order, uint64_t seed) {
     O->c.seed = seed;
 }
 
+/* on = 1: SYMMETRY symmServers (cfg:24, the default); on = 0: a cfg without the SYMMETRY line --
+ * the canonical form is the view under the identity permutation alone (make_perms lists it first).
+ * Call before orc_run. */
+void orc_set_symmetry(void *h, int on) {
+    orc_t *O = (orc_t *)h;
+    make_perms(O->c.n, &O->P);
+    if (!on) O->P.np = 1;
+}
+
 void orc_destroy(void *h) {
     orc_t *O = (orc_t *)h;
     if (!O) return;
@@ -962,9 +971,10 @@ int orc_inv(int n, int V, const int32_t *in, int inv_id) {
 int main(int argc, char **argv) {
     int n = 3, V = 2, E = 3, R = 3, seeded = 0;
     uint32_t mask = 1;
-    int trace = 1, order = 0;
+    int trace = 1, order = 0, symmetry = 1;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-notrace")) trace = 0;
+        else if (!strcmp(argv[i], "-nosymmetry")) symmetry = 0;
         else if (!strcmp(argv[i], "-order")) order = atoi(argv[++i]);
         if (!strcmp(argv[i], "-n")) n = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-V")) V = atoi(argv[++i]);
@@ -976,6 +986,7 @@ int main(int argc, char **argv) {
     }
     void *h = orc_create(n, V, E, R, seeded, 0, mask, trace);
     orc_set_order(h, order, 12345);
+    orc_set_symmetry(h, symmetry);
     int v = orc_run(h, 0);
     uint64_t d[MAXLEVELS], g[MAXLEVELS];
     int L = orc_levels(h, d, g, MAXLEVELS);

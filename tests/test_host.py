@@ -376,3 +376,49 @@ def test_error_variant_specs_recognised():
     assert raftmc.parse_config(cfg_text(), M.commit_past_log(tla)).spec_variant == raftmc.SPEC_COMMIT_PAST_LOG
     with pytest.raises(raftmc.RmcError, match="not kikimo"):
         raftmc.parse_config(cfg_text(), M.split_brain(tla).replace(">= 1 ", ">= 2 "))
+
+
+# (n_servers, n_vals, msg_cap) -> compiled?  rmc_kernels.hip get_kernels: 64 lanes (2,1) (2,2) (3,1) (3,2) (3,3),
+# 128 lanes (3,1) (3,2) (4,1) (4,2) (5,1) (5,2)
+CREATE_CASES = [((1, 1, 64), False), ((3, 0, 64), False), ((2, 3, 64), False), ((4, 3, 64), False),
+                ((5, 3, 64), False), ((5, 1, 64), False), ((4, 3, 0), False), ((5, 3, 128), False),
+                ((2, 1, 128), False), ((3, 3, 128), False), ((6, 1, 0), False), ((0, 1, 0), False),
+                ((5, 1, 0), True), ((5, 2, 128), True), ((4, 2, 0), True), ((3, 3, 64), True), ((3, 2, 128), True),
+                ((3, 1, 8), True), ((2, 2, 0), True)]
+
+
+@pytest.mark.parametrize("combo,compiled", CREATE_CASES, ids=["n%d_v%d_cap%d" % c for c, _ in CREATE_CASES])
+def test_create_refuses_uncompiled_combinations(combo, compiled, capfd):
+    """rmc.h documents exactly the (n_servers, n_vals, message lanes) get_kernels provides: any other is
+    RMC_E_ARG naming the combination, before the device is touched; a compiled one gets as far as the
+    device check (RMC_E_DEVICE on a machine without a GPU)."""
+    n, V, cap = combo
+    lib = raftmc.load_library()
+    c = raftmc.ModelConfig(n_servers=n, n_vals=V, max_election=1, max_restart=3, msg_cap=cap).to_c()
+    h = ctypes.c_void_p()
+    rc = lib.rmc_create(ctypes.byref(c), ctypes.byref(h))
+    err = capfd.readouterr().err
+    if h:
+        lib.rmc_destroy(h)
+    if compiled:
+        assert rc == (0 if has_gpu() else -2), err
+        assert "no compiled kernels" not in err
+    else:
+        assert rc == -1 and not h
+        eff = cap if cap else (64 if n <= 3 else 128)
+        if 1 <= n <= 5:
+            assert f"no compiled kernels for n_servers={n} n_vals={V} msg_cap={eff}" in err
+        else:
+            assert "n_servers must be" in err
+
+
+def test_header_documents_the_compiled_combinations():
+    """The table in rmc.h is the list of CREATE_CASES that create."""
+    text = open(HEADER).read()
+    lanes = {64: re.search(r"64 lanes\s+\(msg_cap 1\.\.64\):\s*(.*)", text).group(1),
+             128: re.search(r"128 lanes \(msg_cap above 64\):\s*(.*)", text).group(1)}
+    doc = {(int(a), int(b), k) for k, row in lanes.items() for a, b in re.findall(r"\((\d),(\d)\)", row)}
+    assert len(doc) == 11
+    for (n, V, cap), compiled in CREATE_CASES:
+        eff = 64 if (cap or (64 if n <= 3 else 128)) <= 64 else 128
+        assert ((n, V, eff) in doc) == compiled, (n, V, cap)

@@ -309,3 +309,76 @@ def test_error_variant_fixtures_recheck(name):
     assert (p.verdict, p.generated, p.distinct, p.queue_left, len(p.trace)) == \
         (g["verdict"], g["generated"], g["distinct"], g["queue_left"], g["trace_len"])
     assert p.levels[:-1] == g["levels"][:-1]
+
+
+# ---- a cfg without SYMMETRY (tests/golden/make_golden_variants.py) --------------------------------
+NOSYM_TOTALS = {  # distinct, generated, depth: the Python oracle with Config(symmetry=False)
+    "nosym_n3_v1_e1_r3": (3172, 11860, 20),
+    "nosym_n2_v1_e2_r3": (2120, 4115, 23),
+    "nosym_n3_v2_e1_r3": (62434, 323836, 28),
+    "nosym_n4_v1_e1_r3": (71333, 373045, 27),
+}
+
+
+@pytest.fixture(scope="module")
+def variants():
+    import importlib.util
+    import sys
+    sys.path.insert(0, GOLDEN)
+    if not os.path.exists(ORC_SO):
+        subprocess.check_call(["make", "-s", "-C", ORC_DIR])
+    spec = importlib.util.spec_from_file_location("mgv", os.path.join(GOLDEN, "make_golden_variants.py"))
+    mgv = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mgv)
+    with open(os.path.join(GOLDEN, "levels_variants.json")) as f:
+        return mgv, json.load(f)
+
+
+@pytest.mark.parametrize("name", sorted(NOSYM_TOTALS) + ["nosym_seeded_n3_v2_e2_r3", "nosym_deadlock_n3_v1_e1_r3"])
+def test_nosym_python_and_c_oracles_agree(variants, name):
+    """Without the SYMMETRY line the canonical form is the view itself: raft_ref.py (symmetry=False) and
+    raft_oracle.c (orc_set_symmetry(h, 0)) agree level by level with each other, with the committed
+    fixture and with the totals the generator pins."""
+    mgv, fixture = variants
+    g = fixture[name]
+    c = mgv.run_c(g["n"], g["V"], g["E"], g["R"], flags=int(g["seeded"]), deadlock=g["check_deadlock"],
+                  symmetry=False)
+    p = R.bfs(R.Config(n=g["n"], V=g["V"], max_election=g["E"], max_restart=g["R"], seeded=g["seeded"],
+                       check_deadlock=g["check_deadlock"], symmetry=False))
+    assert (p.verdict, p.generated, p.distinct, p.depth) == (c["verdict"], c["generated"], c["distinct"], c["depth"])
+    assert (len(p.trace) if p.trace else 0) == c["trace_len"] == g["trace_len"]
+    for k in ("verdict", "generated", "distinct", "depth", "levels", "gen_per_level"):
+        assert c[k] == g[k], k
+    if name in NOSYM_TOTALS:
+        assert (p.levels, p.generated_per_level) == (c["levels"], c["gen_per_level"])
+        assert (p.distinct, p.generated, p.depth) == NOSYM_TOTALS[name] == mgv.NOSYM_TOTALS[name]
+    else:
+        assert (p.queue_left, p.violated) == (g["queue_left"], g["violated"])
+        assert p.levels[:-1] == c["levels"][:len(p.levels) - 1]
+        with open(os.path.join(GOLDEN, "traces_variants.json")) as f:
+            t = json.load(f)[name]
+        assert [(list(k) if k else None, R.state_to_json(s)) for k, s in p.trace] == \
+               [(e["key"], e["state"]) for e in t["steps"]]
+
+
+def test_nosym_distinct_lies_between_the_symmetric_count_and_its_orbit_bound(variants, levels):
+    """Every symmetry class splits into at least one and at most n! views, and neither bound is met:
+    Init is its own orbit, and some state is moved by a permutation."""
+    import math
+    _, fixture = variants
+    for name in NOSYM_TOTALS:
+        g, sym = fixture[name], levels[name[len("nosym_"):]]
+        assert (sym["n"], sym["V"], sym["E"], sym["R"]) == (g["n"], g["V"], g["E"], g["R"])
+        assert sym["distinct"] < g["distinct"] < math.factorial(g["n"]) * sym["distinct"], name
+        assert g["depth"] == sym["depth"], name
+
+
+def test_variant_prefix_fixtures_are_self_consistent(variants):
+    _, fixture = variants
+    for name in ("n5_v2_e1_r3", "bf_n4_v2_e1_r3", "bf_n5_v2_e1_r3"):
+        g = fixture[name]
+        assert g["prefix"] and len(g["gen_per_level"]) == len(g["levels"]) - 1, name
+        assert g["levels"][:2] == [1, 1] and sum(g["levels"]) >= 100_000, name
+    g = fixture["n4_v2_e1_r3"]
+    assert (g["verdict"], g["distinct"], g["generated"], g["depth"], g["max_msgs"]) == ("ok", 212187, 1583824, 38, 21)
+    assert sum(g["levels"]) == g["distinct"] and 1 + sum(g["gen_per_level"]) == g["generated"]
