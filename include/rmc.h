@@ -250,6 +250,61 @@ int rmc_trace_len(void *ctx, uint32_t *len);
 int rmc_trace_state(void *ctx, uint32_t i, int32_t *unpacked, size_t cap_ints,
                     int32_t *action, int32_t *server, int32_t *witness);
 
+/* ---- simulation mode (TLC's -simulate) -------------------------------------------------------
+ * TLC's -simulate runs random behaviours instead of the breadth-first search: each starts at Init,
+ * takes a random enabled successor per step up to -depth states (TLC's default 100) and checks the
+ * INVARIANTs on every state; -seed makes a run repeatable.  rmc_simulate does the same on the GPU, a
+ * wave per walker, for the configurations whose state space cannot be exhausted.  TLC's own random
+ * generator is NOT reproduced: the choice below is this project's definition, fixed so that a CPU
+ * oracle can replay every walk bit for bit.
+ *
+ * A behaviour starts at Init, which is state 1; depth >= 1 is the largest number of states in it.
+ * From state k (k = 1, 2, ...) of walk w, with c the number of successors rmc_successors lists for it
+ * (Next in TLC order, duplicates and self-loops included), the next state is entry (r * c) >> 32 of
+ * that list, r the 32-bit value (arithmetic mod 2^64, step = k - 1):
+ *     z = seed ^ (w * 0x9E3779B97F4A7C15)
+ *     z = z + (step + 1) * 0x9E3779B97F4A7C15
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z = z ^ (z >> 31);   r = z >> 32
+ * A walk ends at the first of: it has `depth` states (the last is not expanded); its state has no
+ * successor (RMC_DEADLOCK with check_deadlock, otherwise the walk just ends: TLC's -deadlock);
+ * evaluating Next at its state fails UpdateTerm's Assert (RMC_ASSERT, the behaviour ends at that
+ * state); the state just chosen violates an INVARIANT in cfg order or raises the evaluation error
+ * (RMC_VIOLATION / RMC_EVAL_ERROR).  Init's invariants are checked once before any walk; an error
+ * there is walk 0, length 1.  The error reported is that of the smallest walk index, under every
+ * schedule.  Accounted walks are 0..err_walk on an error and all of them otherwise: `states` is the
+ * sum of their lengths, `generated` the sum of c over every state they expanded (a state that
+ * asserted or had no successor adds 0) -- both deterministic.  A successor past the message lanes
+ * in an accounted walk fails the call with RMC_E_CAPACITY.
+ *
+ * The host runs batches of batch_walks walkers (0 = auto: up to 2^18, fewer while the device log of
+ * the steps' slot keys, batch x (depth - 1) x 2 B, would pass 64 MiB) and stops after the first batch
+ * that holds an error.  Single GPU only: world_size > 1 or virtual_shards > 1, depth == 0 or
+ * num_walks == 0 is RMC_E_ARG.  The call touches none of the BFS state and may come on a fresh
+ * context, between BFS steps or after a run.  After an error rmc_trace_len / rmc_trace_state return
+ * the erring behaviour (replayed from Init with the logged keys) until the next BFS error, rmc_reset
+ * or rmc_simulate.  lens_out (num_walks) and keys_out (num_walks x (depth - 1), rmc_successors' key
+ * format, 0 past a walk's end) may be NULL; walks that are not accounted stay 0. */
+typedef struct rmc_sim_config {
+    uint64_t num_walks;
+    uint64_t seed;        /* TLC -seed */
+    uint32_t depth;       /* TLC -depth */
+    uint32_t batch_walks; /* walkers per launch, 0 = auto */
+} rmc_sim_config;
+typedef struct rmc_sim_result {
+    int32_t status;       /* RMC_DONE, or the error status of err_walk */
+    int32_t violated;     /* invariant bit index, -1 if none */
+    uint64_t walks, states, generated; /* accounted, as defined above */
+    uint64_t err_walk;    /* valid when status != RMC_DONE */
+    uint32_t err_len;
+    uint32_t longest;     /* longest accounted behaviour */
+    uint64_t ended_early; /* accounted walks that ended in a state without successors */
+    double seconds;
+} rmc_sim_result;
+/* Returns the result's status, or a negative RMC_E_* code. */
+int rmc_simulate(void *ctx, const rmc_sim_config *sc, rmc_sim_result *res, uint32_t *lens_out, uint32_t *keys_out);
+
 /* Measurement support (bench.py): the random-probe peak of the seen-set layout -- `probes`
  * one-slot reads of 16-B slots at uniformly random indices of a 2^table_log2-slot table,
  * best of 3 timed launches; no model-checking state is touched. */

@@ -540,6 +540,12 @@ struct rmc_ctx {
     int32_t *d_inv = nullptr;
     unsigned long long *d_err1 = nullptr;
     uint32_t *d_flags1 = nullptr;
+    // simulation mode (simulate): Init's record, per-walk outputs and key log of a batch, error words
+    uint32_t *d_sim_init = nullptr, *d_sim_len = nullptr, *d_sim_gen = nullptr, *d_sim_end = nullptr;
+    uint16_t *d_sim_keys = nullptr;
+    unsigned long long *d_sim_err = nullptr;
+    uint64_t sim_walks_cap = 0, sim_keys_cap = 0;
+    bool trace_from_sim = false;  // `trace` holds rmc_simulate's erring behaviour, not a run's counterexample
     unsigned long long *d_red = nullptr, *h_red = nullptr;  // collective scratch (RED_CAP values)
     static constexpr int RED_CAP = 64 * (2 * 64 + 8) + (2 * 64 + 8);  // a W x K gathered count matrix + one row
 
@@ -1196,6 +1202,8 @@ struct rmc_ctx {
         dfree(d_info); dfree(d_nat2id); dfree(d_gmsg); dfree(d_seeds);
         dfree(d_one); dfree(d_init_rec); dfree(d_init_fp); dfree(d_out); dfree(d_keys); dfree(d_cnt1); dfree(d_fp1); dfree(d_inv); dfree(d_err1);
         dfree(d_flags1); dfree(d_red);
+        dfree(d_sim_init); dfree(d_sim_len); dfree(d_sim_gen); dfree(d_sim_end); dfree(d_sim_keys); dfree(d_sim_err);
+        sim_walks_cap = sim_keys_cap = 0;
         if (h_red) (void)hipHostFree(h_red);
         h_red = nullptr;
         hx_send.release();
@@ -3309,6 +3317,12 @@ struct rmc_ctx {
     void build_trace() {
         std::vector<uint16_t> slots = path_slots(err_ref, nullptr);
         if (err_last_slot != KEY_NONE) slots.push_back((uint16_t)err_last_slot);
+        replay_trace(slots);
+        trace_from_sim = false;
+    }
+
+    // the behaviour that takes the successors with these slot keys from Init on -> trace
+    void replay_trace(const std::vector<uint16_t> &slots) {
         trace.clear();
         std::vector<uint32_t> rec = init_record();
         trace.push_back({unpack(rec.data()), -1, -1, -1});
@@ -3324,6 +3338,150 @@ struct rmc_ctx {
             trace.push_back({unpack(rec.data()), (int32_t)key_action(sk), (int32_t)key_server(sk),
                              (int32_t)key_witness(sk)});
         }
+    }
+
+    // ---- simulation mode (rmc_simulate; TLC's -simulate) ---------------------------------------
+    // Batches of walkers (k_walk), each batch one launch; the host adds up the accounted walks'
+    // counters and stops after the first batch that holds an error.  It owns its buffers and reads
+    // none of the BFS state (seen set, ring, levels, counters): the only members it shares with a
+    // run are the single-state hook scratch (the trace replay) and `trace` itself.
+    static constexpr uint64_t SIM_KEYS_BUDGET = 64ull << 20;  // device bytes of a batch's key log at most
+    static constexpr uint64_t SIM_AUTO_BATCH = 1ull << 18;    // walkers of an auto batch at most
+    void sim_reserve(uint64_t walks, uint64_t keys) {
+        if (!d_sim_init) {
+            d_sim_init = dmalloc<uint32_t>(RECW);
+            d_sim_err = dmalloc<unsigned long long>(2);
+        }
+        if (walks > sim_walks_cap) {
+            dfree(d_sim_len); dfree(d_sim_gen); dfree(d_sim_end);
+            sim_walks_cap = 0;
+            d_sim_len = dmalloc<uint32_t>(walks);
+            d_sim_gen = dmalloc<uint32_t>(walks);
+            d_sim_end = dmalloc<uint32_t>(walks);
+            sim_walks_cap = walks;
+        }
+        if (keys > sim_keys_cap) {
+            dfree(d_sim_keys);
+            sim_keys_cap = 0;
+            d_sim_keys = dmalloc<uint16_t>(keys);
+            sim_keys_cap = keys;
+        }
+    }
+
+    int simulate(const rmc_sim_config &sc, rmc_sim_result *res, uint32_t *lens_out, uint32_t *keys_out) {
+        if (multi || W > 1 || cfg.virtual_shards > 1)
+            throw Fail(RMC_E_ARG, "simulate: single GPU only (world_size and virtual_shards at most 1)");
+        if (sc.depth == 0 || sc.num_walks == 0) throw Fail(RMC_E_ARG, "simulate: depth and num_walks must be at least 1");
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint64_t dm1 = sc.depth - 1u;
+        uint64_t batch = sc.batch_walks;
+        if (!batch) {  // auto: large launches, the key log of one under its budget
+            batch = std::min<uint64_t>(sc.num_walks, SIM_AUTO_BATCH);
+            if (dm1 && batch * dm1 * 2 > SIM_KEYS_BUDGET) batch = std::max<uint64_t>(1, SIM_KEYS_BUDGET / (dm1 * 2));
+        }
+        batch = std::min<uint64_t>(batch, sc.num_walks);
+        if (batch > 0x7FFFFFFFull || batch * std::max<uint64_t>(dm1, 1) > (1ull << 40))
+            throw Fail(RMC_E_ARG, "simulate: batch_walks x depth too large");
+        HIPCHK(hipStreamSynchronize(stream));
+        sim_reserve(batch, batch * std::max<uint64_t>(dm1, 1));
+        if (trace_from_sim) trace.clear();
+        trace_from_sim = false;
+        std::memset(res, 0, sizeof *res);
+        res->status = RMC_DONE;
+        res->violated = -1;
+        if (lens_out) std::memset(lens_out, 0, sc.num_walks * 4);
+        if (keys_out && dm1) std::memset(keys_out, 0, sc.num_walks * dm1 * 4);
+        auto finish = [&] {
+            res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            return res->status;
+        };
+
+        // Init: its record for the walkers, its invariants once before any walk
+        const std::vector<uint32_t> init = init_record();
+        HIPCHK(hipMemcpy(d_sim_init, init.data(), RECW * 4, hipMemcpyHostToDevice));
+        KParams P = base(sh[0]);
+        P.front = d_sim_init;
+        {
+            int32_t iv[7];
+            ks.inv_states(P, 1, d_inv, stream);
+            HIPCHK(hipMemcpyAsync(iv, d_inv, sizeof iv, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            for (uint32_t o = inv_order; o; o >>= 4) {
+                const int b = (int)(o & 15u) - 1;
+                if (iv[b] == 1) continue;
+                res->status = iv[b] == 0 ? RMC_VIOLATION : RMC_EVAL_ERROR;
+                res->violated = b;
+                res->walks = res->states = 1;
+                res->err_walk = 0;
+                res->err_len = res->longest = 1;
+                if (lens_out) lens_out[0] = 1;
+                replay_trace({});
+                trace_from_sim = true;
+                return finish();
+            }
+        }
+
+        std::vector<uint32_t> hlen(batch), hgen(batch), hend(batch);
+        std::vector<uint16_t> hkeys;
+        for (uint64_t w0 = 0; w0 < sc.num_walks; w0 += batch) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(batch, sc.num_walks - w0);
+            HIPCHK(hipMemsetAsync(d_sim_err, 0xFF, 16, stream));
+            HIPCHK(hipMemsetAsync(d_sim_end, 0xFF, (size_t)n * 4, stream));
+            WalkParams wp{};
+            wp.init_rec = d_sim_init;
+            wp.walk0 = w0;
+            wp.seed = sc.seed;
+            wp.n = n;
+            wp.depth = sc.depth;
+            wp.len = d_sim_len; wp.gen = d_sim_gen; wp.end = d_sim_end;
+            wp.keys = d_sim_keys;
+            wp.err = d_sim_err;
+            ks.walk(P, wp, stream);
+            HIPCHK(hipGetLastError());
+            unsigned long long e[2];
+            HIPCHK(hipMemcpyAsync(e, d_sim_err, sizeof e, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(hlen.data(), d_sim_len, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(hgen.data(), d_sim_gen, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(hend.data(), d_sim_end, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            const bool erred = e[0] != ~0ull;
+            const uint32_t acc = erred ? (uint32_t)(e[0] >> 32) + 1u : n;  // accounted walks of this batch
+            if (e[1] < acc) throw Fail(RMC_E_CAPACITY, "simulate: a successor exceeds msg_cap messages");
+            if (keys_out && dm1) {
+                hkeys.resize((size_t)acc * dm1);
+                HIPCHK(hipMemcpy(hkeys.data(), d_sim_keys, hkeys.size() * 2, hipMemcpyDeviceToHost));
+            }
+            for (uint32_t i = 0; i < acc; i++) {
+                const uint32_t end = hend[i] & 0xFFu;
+                if (end == WALK_DROPPED) throw Fail(RMC_E_STATE, "simulate: an accounted walk did not run to its end");
+                res->walks++;
+                res->states += hlen[i];
+                res->generated += hgen[i];
+                res->longest = std::max(res->longest, hlen[i]);
+                if (end == WALK_STUCK || end == WALK_DEADLOCK) res->ended_early++;
+                if (lens_out) lens_out[w0 + i] = hlen[i];
+                if (keys_out)
+                    for (uint32_t k = 0; k + 1 < hlen[i]; k++) {
+                        const uint32_t sk = hkeys[(size_t)i * dm1 + k];
+                        keys_out[(w0 + i) * dm1 + k] = (key_server(sk) << 24) | (key_action(sk) << 16) | key_witness(sk);
+                    }
+            }
+            if (!erred) continue;
+            const uint32_t ei = acc - 1, end = hend[ei] & 0xFFu;
+            res->err_walk = w0 + ei;
+            res->err_len = (uint32_t)e[0];
+            if (res->err_len != hlen[ei]) throw Fail(RMC_E_STATE, "simulate: the error word and the walk's length differ");
+            res->status = end == WALK_DEADLOCK ? RMC_DEADLOCK : end == WALK_ASSERT ? RMC_ASSERT
+                        : end == WALK_VIOLATION ? RMC_VIOLATION : RMC_EVAL_ERROR;
+            if (end == WALK_VIOLATION || end == WALK_EVAL) res->violated = (int32_t)(hend[ei] >> 8);
+            std::vector<uint16_t> slots(res->err_len - 1u);
+            if (!slots.empty())
+                HIPCHK(hipMemcpy(slots.data(), d_sim_keys + (size_t)ei * dm1, slots.size() * 2, hipMemcpyDeviceToHost));
+            replay_trace(slots);
+            trace_from_sim = true;
+            break;
+        }
+        return finish();
     }
 
     // ---- checkpoint / resume (rmc_checkpoint, rmc_resume) --------------------------------
@@ -3693,6 +3851,7 @@ struct rmc_ctx {
         }
         // (the clears are stream-ordered before the next run's first kernel: no wait here)
         trace.clear();
+        trace_from_sim = false;
         inited = finished = false;
         status = RMC_OK;
         depth = 0;
@@ -3948,6 +4107,12 @@ int rmc_release_device(void *ctx) {
     c->release(true);
     c->device_released = true;
     return RMC_OK;
+}
+
+int rmc_simulate(void *ctx, const rmc_sim_config *sc, rmc_sim_result *res, uint32_t *lens_out, uint32_t *keys_out) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    if (!sc || !res) return RMC_E_ARG;
+    return guarded(c, [&] { return c->simulate(*sc, res, lens_out, keys_out); });
 }
 
 int rmc_successors(void *ctx, const int32_t *unpacked, int32_t *out, size_t stride, uint32_t cap, uint32_t *keys,

@@ -211,6 +211,35 @@ struct KParams {
     uint32_t *out_count;
 };
 
+// Simulation mode (rmc_simulate; TLC's -simulate): one batch of seeded random walks, a wave per walker.
+// Walk i of the batch is walk `walk0 + i` of the call; it starts at Init (init_rec, RECW_MAX words) and
+// takes at most `depth` states.  From state k (k = 1: Init) with c successors in TLC order it moves to
+// successor walk_choice(seed, walk, k - 1, c) -- the project's own definition (include/rmc.h), not TLC's
+// random generator.
+enum WalkEnd : uint32_t {
+    WALK_DEPTH = 0,      // the depth bound
+    WALK_STUCK = 1,      // a state without successors, deadlock checking off
+    WALK_DEADLOCK = 2,   // ... deadlock checking on
+    WALK_ASSERT = 3,     // UpdateTerm's Assert (tla:185) fails while Next is evaluated
+    WALK_VIOLATION = 4,  // the chosen state violates invariant (end >> 8)
+    WALK_EVAL = 5,       // ... or raises the evaluation error in it
+    WALK_DROPPED = 0xFFu // not run to its end: an error of a smaller walk index was already recorded
+};
+struct WalkParams {
+    const uint32_t *init_rec;
+    uint64_t walk0, seed;
+    uint32_t n, depth;
+    uint32_t *len, *gen, *end;   // per walk of the batch: states, successors generated, WalkEnd (| invariant << 8)
+    uint16_t *keys;              // [n][depth - 1] slot key of every step taken
+    unsigned long long *err;     // [0] atomic-min (i << 32 | length) of the erring walks; [1] atomic-min index
+                                 // of the walks that met a successor past the message lanes (all ones: none)
+};
+// r of include/rmc.h's definition, then (r * c) >> 32
+RMC_HD uint32_t walk_choice(uint64_t seed, uint64_t walk, uint32_t step, uint32_t c) {
+    const uint64_t z = (seed ^ (walk * 0x9e3779b97f4a7c15ULL)) + ((uint64_t)step + 1) * 0x9e3779b97f4a7c15ULL;
+    return (uint32_t)(((mix64(z) >> 32) * (uint64_t)c) >> 32);
+}
+
 struct KernelSet {
     int N, V, MR, MCAP, CCW, RECW_MAX, maxsucc;
     int ctxw;                                                 // hash-context words per parent (split chunks)
@@ -231,6 +260,7 @@ struct KernelSet {
                         uint32_t round, uint32_t W, uint32_t self, uint64_t g0, hipStream_t);
     void (*local_flags)(const KParams &, uint64_t np, Seen, const ESlot *OT, uint32_t round, uint32_t W,
                         uint32_t self, uint64_t g0, unsigned long long *inserted, hipStream_t);
+    void (*walk)(const KParams &, const WalkParams &, hipStream_t);  // simulation: one batch of random walks
     void (*fp_states)(const KParams &, uint64_t n, hipStream_t);  // fp of front[0..n) -> fp
     void (*inv_states)(const KParams &, uint64_t n, int32_t *out, hipStream_t); // per state: 1/0/-1 for inv_mask bits
     // host codec of the packed core (rmc_spec.h Codec)

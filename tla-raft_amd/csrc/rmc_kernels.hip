@@ -3803,6 +3803,141 @@ __global__ __launch_bounds__(256) void k_local_flags(KParams P, Seen seen, const
     block_count_add(mine, inserted);
 }
 
+// ---- simulation mode: seeded random walks (rmc_simulate; TLC's -simulate) ------------------------
+// A 64-lane wave per walker, persistent: the wave takes walks b, b + grid, ... of the batch and loops
+// over a walk's steps inside the launch.  A step is k_expand's M_SINGLE expansion without the
+// fingerprints: load the state, evaluate every candidate on the lanes, rank the enabled ones in TLC
+// order, then -- instead of writing all of them out -- rebuild only successor walk_choice(...) of that
+// list, check its invariants and log its slot key.  There is no seen set, no election and no hand-off
+// between walkers but two atomic-min words: the smallest (walk, length) that ended in an error, which
+// every walker reads once per step (a walk above an erring one may stop at once; a walk below it always
+// runs to its end, so the error reported and the counters of walks 0 .. err are the same under every
+// schedule), and the smallest walk that met a successor past the message lanes.
+// The walker's current and next records (ping-pong) stay in LDS, read and written through the same
+// load_parent / write_record as frontier records: P.front is pointed at them, fixed stride, no ring.
+template <int N, int V, int MR, bool BFV>
+__global__ __launch_bounds__(64) void k_walk(KParams P, WalkParams Wp) {
+    using S = Spec<N, V, MR>;
+    using Lo = Layout<N, V>;
+    constexpr int NC = MR + 1 + (BFV ? MR : 0);  // candidates per lane: messages, slot, BecomeFollower
+    __shared__ uint32_t pcore[Lo::NW + N];
+    __shared__ uint32_t srec[2 * S::RECW_MAX];
+    extern __shared__ uint32_t sBM[];            // bitmap of the state's message ids (P.t.bmw words)
+    const int lane = threadIdx.x;
+    P.front = srec;
+    P.foff = nullptr;
+    P.rcap = ~0ull;
+    const uint32_t dm1 = Wp.depth - 1u;
+    for (uint32_t i = blockIdx.x; i < Wp.n; i += gridDim.x) {
+        // (this wave's later walks have larger indices still: all of them are past an error below i)
+        if ((uint32_t)(__hip_atomic_load(&Wp.err[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) < i) break;
+        const uint64_t walk = Wp.walk0 + i;
+        __syncthreads();
+        for (int k = lane; k < S::RECW_MAX; k += 64) srec[k] = Wp.init_rec[k];
+        __syncthreads();
+        uint32_t cur = 0, len = 1, gen = 0, end = WALK_DEPTH;
+        while (len < Wp.depth) {
+            if ((uint32_t)(__hip_atomic_load(&Wp.err[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) < i) {
+                end = WALK_DROPPED;
+                break;
+            }
+            Wave<N, V, MR> W;
+            load_parent<N, V, MR, false>(P, (uint64_t)cur * S::RECW_MAX, lane, W, nullptr, nullptr, pcore);
+            msg_bitmap<N, V, MR>(sBM, P.t.bmw, W, lane);
+            W.bm = sBM;
+            Succ<N, V, MR> cand[NC];
+            uint32_t akey = KEY_NONE;
+            int ln = lane;  // (opaque, as in k_expand: what the evaluation derives from it is not hoisted)
+            asm volatile("" : "+v"(ln));
+            uint32_t mid[MR], sid[N - 1];
+            {
+                uint32_t snat[N - 1];
+                slot_nats<N, V, MR>(P, W, ln, snat);
+#pragma unroll
+                for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
+#pragma unroll
+                for (int q = 0; q < N - 1; q++) sid[q] = nat_lookup(P, snat[q]);
+            }
+#pragma unroll
+            for (int r = 0; r < MR; r++)
+                eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey, nullptr, mid[r]);
+            eval_slot<N, V, MR>(P, W, ln, cand[MR], nullptr, sid);
+            // rank of every enabled successor in TLC order, and their number c
+            uint64_t en[NC];
+            uint32_t total = 0;
+#pragma unroll
+            for (int r = 0; r < NC; r++) {
+                en[r] = __ballot(cand[r].key != KEY_NONE);
+                total += (uint32_t)__popcll(en[r]);
+            }
+            uint32_t rank[NC];
+#pragma unroll
+            for (int r = 0; r < NC; r++) rank[r] = 0;
+#pragma unroll
+            for (int q = 0; q < NC; q++) {
+                for (uint64_t m = en[q]; m; m &= m - 1) {
+                    const int t = __ffsll((unsigned long long)m) - 1;
+                    const uint32_t kt = rdlane(cand[q].key, t);
+#pragma unroll
+                    for (int r = 0; r < NC; r++) rank[r] += kt < cand[r].key ? 1u : 0u;
+                }
+            }
+            bool ovf = false;
+#pragma unroll
+            for (int r = 0; r < NC; r++) ovf |= cand[r].key != KEY_NONE && W.nm + cand[r].nadd > (uint32_t)S::MCAP;
+            if (__ballot(ovf)) {  // the expansion's capacity rule: the call fails, the walk stops before any write
+                if (lane == 0) atomicMin(&Wp.err[1], (unsigned long long)i);
+                end = WALK_DROPPED;
+                break;
+            }
+            if (__ballot(akey != KEY_NONE)) { end = WALK_ASSERT; break; }
+            if (total == 0) { end = P.check_deadlock ? WALK_DEADLOCK : WALK_STUCK; break; }
+            gen += total;
+            const uint32_t idx = walk_choice(Wp.seed, walk, len - 1u, total);
+            // the one candidate of rank idx: each lane's own copy of it, then the lane that holds it
+            Succ<N, V, MR> ch = cand[MR];
+            bool hit = false;
+#pragma unroll
+            for (int r = 0; r < NC; r++) {
+                const bool h = cand[r].key != KEY_NONE && rank[r] == idx;
+                if (h) ch = cand[r];
+                hit |= h;
+            }
+            const uint64_t hm = __ballot(hit);
+            if (!hm) { end = WALK_DROPPED; break; }  // (unreachable: the ranks are a permutation of 0 .. c - 1)
+            const int t = __ffsll((unsigned long long)hm) - 1;
+            const uint32_t key = rdlane(ch.key, t);
+            if (lane == 0) Wp.keys[(uint64_t)i * dm1 + (len - 1u)] = (uint16_t)key;
+            len++;
+            if (rdlane(ch.self ? 1u : 0u, t)) continue;  // the state itself: it stays, its invariants held
+            const uint32_t nxt = cur ^ 1u;
+            write_record<N, V, MR>(W, ch, t, lane, srec + nxt * S::RECW_MAX);
+            __syncthreads();
+            cur = nxt;
+            uint32_t c[Lo::NW];
+#pragma unroll
+            for (int w = 0; w < Lo::NW; w++) c[w] = rdlane(ch.c[w], t);
+            const uint32_t nm2 = W.nm + rdlane(ch.nadd, t);
+            c[Lo::W_MISC] = (c[Lo::W_MISC] & ~0xFF0000u) | (nm2 << 16);
+            int which = 0;
+            const MsgView mv{srec, (uint64_t)(cur * S::RECW_MAX + S::CCW), ~0ull, nm2, 0u, 0u, 0u, P.t.info};
+            const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
+            if (iv != 1) {
+                end = (iv == 0 ? WALK_VIOLATION : WALK_EVAL) | ((uint32_t)which << 8);
+                break;
+            }
+        }
+        if (lane == 0) {
+            const uint32_t e = end & 0xFFu;
+            if (e >= WALK_DEADLOCK && e != WALK_DROPPED)
+                atomicMin(&Wp.err[0], ((unsigned long long)i << 32) | (unsigned long long)len);
+            Wp.len[i] = len;
+            Wp.gen[i] = gen;
+            Wp.end[i] = end;
+        }
+    }
+}
+
 static inline unsigned grid_for(uint64_t n) {
     const uint64_t cap = 256ull * RMC_GRID_PER_CU;  // one-wave blocks per CU (default 32) on 256 CUs
     return (unsigned)(n < cap ? (n ? n : 1) : cap);
@@ -3890,6 +4025,9 @@ struct Launch {
                            dim3(blocks ? (unsigned)(blocks < 16384ull ? blocks : 16384ull) : 1u), dim3(256), 0, s, P,
                            seen, OT, round, W, self, g0, inserted);
     }
+    static void walk(const KParams &P, const WalkParams &wp, hipStream_t s) {
+        hipLaunchKernelGGL((k_walk<N, V, MR, BFV>), dim3(grid_for(wp.n)), dim3(64), bm_bytes(P), s, P, wp);
+    }
     static void fps(const KParams &P, uint64_t n, hipStream_t s) {
         hipLaunchKernelGGL((k_fp_states<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n);
     }
@@ -3916,6 +4054,7 @@ static void fill(KernelSet *ks) {
     ks->commit_split = &Launch<N, V, MR, BFV>::commit_split;
     ks->local_elect = &Launch<N, V, MR, BFV>::local_elect;
     ks->local_flags = &Launch<N, V, MR, BFV>::local_flags;
+    ks->walk = &Launch<N, V, MR, BFV>::walk;
     ks->fp_states = &Launch<N, V, MR>::fps;
     ks->inv_states = &Launch<N, V, MR>::invs;
     ks->encode = &Launch<N, V, MR>::enc;

@@ -1,10 +1,12 @@
 // raftmc -- TLC-compatible command line over librmc (the drop-in for myrun.sh:3).
 //
 //   raftmc [-deadlock] [-workers N] [-config Raft.cfg] [-device D] [-gpus N] [-msgcap C] [-seenlog2 K] Raft.tla
+//   raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config Raft.cfg] [-device D] [-msgcap C] Raft.tla
 //
 // Accepts the flags myrun.sh passes to TLC (myrun.sh:3), reads the same Raft.tla /
 // Raft.cfg, and prints TLC's result lines (states generated, distinct states, depth,
-// the counterexample) so that parsers of raft.log keep working.  GPU-specific lines
+// the counterexample) so that parsers of raft.log keep working.  -simulate is TLC's simulation mode:
+// seeded random behaviours of at most -depth states instead of the breadth-first search (rmc_simulate).  GPU-specific lines
 // are printed after TLC's block.  Exit codes follow TLC's (0 ok, 11 deadlock,
 // 12 safety violation, 14 Assert, 75 evaluation error, 150/151 spec/config errors).
 #include <fcntl.h>
@@ -219,7 +221,14 @@ struct Printer {
 int usage(const char *msg) {
     std::fprintf(stderr, "raftmc: %s\nusage: raftmc [-deadlock] [-workers N] [-config FILE.cfg] [-device D] "
                          "[-gpus N [-onerank] [-shardmin K]] [-msgcap C] [-seenlog2 K] [-checkpoint MIN] [-metadir DIR] "
-                         "[-recover DIR] FILE.tla\n", msg);
+                         "[-recover DIR] FILE.tla\n"
+                         "       raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config FILE.cfg] [-device D] "
+                         "[-msgcap C] FILE.tla\n"
+                         "  -simulate  random behaviours instead of the breadth-first search; num=N of them (default "
+                         "1000000; TLC's default is unbounded)\n"
+                         "  -depth D   states per behaviour at most (default 100, as TLC)\n"
+                         "  -seed S    seed of the walks (default: from the clock; printed); the generator is this "
+                         "project's own, not TLC's\n", msg);
     return 150;
 }
 
@@ -409,6 +418,9 @@ int main(int argc, char **argv) {
     double progress_s = 60.0;           // TLC reports Progress once a minute (and at the end)
     double ckpt_minutes = 30.0;         // TLC -checkpoint: minutes between checkpoints (0 = never)
     std::string metadir, recover_dir;   // TLC -metadir / -recover: where checkpoints go / come from
+    bool simulate = false, ckpt_given = false, seed_given = false, sim_bad = false;  // TLC -simulate [num=N]
+    unsigned long long sim_num = 1000000, sim_seed = 0;  // (TLC's -simulate is unbounded without num=)
+    long long sim_depth = 100;                           // TLC -depth
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *f) -> const char * {
@@ -424,7 +436,18 @@ int main(int argc, char **argv) {
         else if (a == "-shardmin") shardmin = std::strtoull(need("-shardmin"), nullptr, 10);
         else if (a == "-msgcap") msgcap = std::atoi(need("-msgcap"));
         else if (a == "-seenlog2") seenlog2 = std::atoi(need("-seenlog2"));
-        else if (a == "-checkpoint") ckpt_minutes = std::atof(need("-checkpoint"));
+        else if (a == "-checkpoint") { ckpt_minutes = std::atof(need("-checkpoint")); ckpt_given = true; }
+        else if (a == "-simulate") {
+            simulate = true;
+            if (i + 1 < argc && std::strchr(argv[i + 1], '=')) {  // num=N
+                const std::string v = argv[++i];
+                char *end = nullptr;
+                const bool digits = v.size() > 4 && v.compare(0, 4, "num=") == 0 && isdigit((unsigned char)v[4]);
+                sim_num = digits ? std::strtoull(v.c_str() + 4, &end, 10) : 0;
+                if (!digits || *end || sim_num == 0) sim_bad = true;
+            }
+        } else if (a == "-depth") sim_depth = std::atoll(need("-depth"));
+        else if (a == "-seed") { sim_seed = (unsigned long long)std::strtoll(need("-seed"), nullptr, 10); seed_given = true; }
         else if (a == "-metadir") metadir = need("-metadir");
         else if (a == "-recover") recover_dir = need("-recover");
         else if (a == "-progress") progress_s = std::atof(need("-progress"));
@@ -432,6 +455,15 @@ int main(int argc, char **argv) {
         else if (a.size() > 4 && a.compare(a.size() - 4, 4, ".tla") == 0) tla_path = a;
         else if (a[0] != '-' && tla_path.empty()) tla_path = a + ".tla";
         else return usage(("unsupported option " + a).c_str());
+    }
+    if (simulate) {  // refused before anything touches a device
+        if (sim_bad) return usage("-simulate takes num=N with N >= 1");
+        if (sim_depth < 1 || sim_depth > 0x7FFFFFFFll) return usage("-depth must be at least 1");
+        if (gpus > 1 || onerank) return usage("-simulate runs on one GPU (no -gpus)");
+        if (!recover_dir.empty()) return usage("-simulate cannot be combined with -recover");
+        if (ckpt_given) return usage("-simulate cannot be combined with -checkpoint");
+        if (!seed_given)
+            sim_seed = (unsigned long long)std::chrono::system_clock::now().time_since_epoch().count();
     }
     if (tla_path.empty()) return usage("missing spec file");
     if (gpus < 1 || gpus > 64) return usage("-gpus must be 1..64");
@@ -473,12 +505,65 @@ int main(int argc, char **argv) {
     cfg.shard_min_states = shardmin;
 
     std::printf("raftmc (MI355X-native model checker for kikimo/tla-raft) -- TLC-compatible output\n");
-    std::printf("Running breadth-first search Model-Checking on %d GPU%s (TLC -workers %d order: 1).\n", gpus,
-                gpus > 1 ? "s" : "", workers);
+    if (simulate)
+        std::printf("Running Random Simulation with seed %llu on 1 GPU (%llu behaviours of at most %lld states; the "
+                    "generator is raftmc's own, not TLC's).\n", sim_seed, sim_num, sim_depth);
+    else
+        std::printf("Running breadth-first search Model-Checking on %d GPU%s (TLC -workers %d order: 1).\n", gpus,
+                    gpus > 1 ? "s" : "", workers);
     std::printf("Parsing file %s\n", tla_path.c_str());
     std::printf("Semantic processing of module %s\n", pm.module.c_str());
     for (const auto &c : pm.ignored_constants) std::printf("(ignoring assignment to undeclared constant %s)\n", c.c_str());
     std::printf("Starting... (%s)\n", now_str().c_str());
+    // TLC's error lines and "The behavior up to this point is:" block for the context's trace; returns
+    // TLC's exit code for the status
+    auto print_error = [&](void *ctx, const rmc_config &cfg, int status, int violated, uint32_t trace_len) -> int {
+        int exit_code = 0;
+        if (status == RMC_VIOLATION) {
+            // the name the cfg used for the violated invariant (Inv and LeaderHasAllCommittedEntries share bit 0)
+            std::string name = kInvNames[violated];
+            for (const std::string &n : pm.invariant_names)
+                if ((violated == 0 && (n == "Inv" || n == "LeaderHasAllCommittedEntries")) || n == kInvNames[violated])
+                    name = n;
+            std::printf("Error: Invariant %s is violated.\n", name.c_str());
+            exit_code = 12;
+        } else if (status == RMC_ASSERT) {
+            std::printf("Error: The first argument of Assert evaluated to FALSE; the second argument was:\n\"split brain\"\n");
+            exit_code = 14;
+        } else if (status == RMC_EVAL_ERROR) {
+            std::printf("Error: Evaluating invariant %s failed.\nAttempted to apply a tuple to an index out of its domain "
+                        "(logs[p][index], %s.tla line 499).\n", kInvNames[violated], pm.module.c_str());
+            exit_code = 75;
+        } else if (status == RMC_DEADLOCK) {
+            std::printf("Error: Deadlock reached.\n");
+            exit_code = 11;
+        }
+        std::printf("Error: The behavior up to this point is:\n");
+        std::vector<std::string> names(kActionNames, kActionNames + 13);
+        names.insert(names.end(), kBfNames, kBfNames + 3);  // 13..15
+        std::vector<Loc> locs = action_locations(tla, names);
+        Printer pr{pm, cfg.n_servers, cfg.n_vals};
+        std::vector<int32_t> buf(RMC_UNPACKED_INTS(5, 3, 256));
+        std::vector<int32_t> prev_role(cfg.n_servers, 0);
+        for (uint32_t i = 0; i < trace_len; i++) {
+            int32_t a, s, w;
+            int nints = rmc_trace_state(ctx, i, buf.data(), buf.size(), &a, &s, &w);
+            if (nints < 0) break;
+            if (a < 0) std::printf("State %u: <Initial predicate>\n", i + 1);
+            else {
+                const int an = (a == 12 && s >= 0 && s < cfg.n_servers) ? 13 + prev_role[s] : a;  // role: 0 F, 1 C, 2 L
+                const Loc &L = locs[an];
+                if (L.l0)
+                    std::printf("State %u: <%s line %d, col %d to line %d, col %d of module %s>\n", i + 1,
+                                names[an].c_str(), L.l0, L.c0, L.l1, L.c1, pm.module.c_str());
+                else
+                    std::printf("State %u: <%s(%s)>\n", i + 1, names[an].c_str(), pm.servers[s].c_str());
+            }
+            for (int q = 0; q < cfg.n_servers; q++) prev_role[q] = buf[2 * cfg.n_servers + q];  // unpacked: vf, ct, role
+            std::printf("%s\n", pr.state(buf.data()).c_str());
+        }
+        return exit_code;
+    };
     auto check = [&](const rmc_config &cfg) -> int {
     const auto t0 = std::chrono::steady_clock::now();
     void *ctx = nullptr;
@@ -571,53 +656,8 @@ int main(int argc, char **argv) {
     rmc_result res;
     rmc_get_result(ctx, &res);
     int exit_code = 0;
-    if (res.status == RMC_DONE) {
-        std::printf("Model checking completed. No error has been found.\n");
-    } else {
-        if (res.status == RMC_VIOLATION) {
-            // the name the cfg used for the violated invariant (Inv and LeaderHasAllCommittedEntries share bit 0)
-            std::string name = kInvNames[res.violated];
-            for (const std::string &n : pm.invariant_names)
-                if ((res.violated == 0 && (n == "Inv" || n == "LeaderHasAllCommittedEntries")) || n == kInvNames[res.violated])
-                    name = n;
-            std::printf("Error: Invariant %s is violated.\n", name.c_str());
-            exit_code = 12;
-        } else if (res.status == RMC_ASSERT) {
-            std::printf("Error: The first argument of Assert evaluated to FALSE; the second argument was:\n\"split brain\"\n");
-            exit_code = 14;
-        } else if (res.status == RMC_EVAL_ERROR) {
-            std::printf("Error: Evaluating invariant %s failed.\nAttempted to apply a tuple to an index out of its domain "
-                        "(logs[p][index], %s.tla line 499).\n", kInvNames[res.violated], pm.module.c_str());
-            exit_code = 75;
-        } else if (res.status == RMC_DEADLOCK) {
-            std::printf("Error: Deadlock reached.\n");
-            exit_code = 11;
-        }
-        std::printf("Error: The behavior up to this point is:\n");
-        std::vector<std::string> names(kActionNames, kActionNames + 13);
-        names.insert(names.end(), kBfNames, kBfNames + 3);  // 13..15
-        std::vector<Loc> locs = action_locations(tla, names);
-        Printer pr{pm, cfg.n_servers, cfg.n_vals};
-        std::vector<int32_t> buf(RMC_UNPACKED_INTS(5, 3, 256));
-        std::vector<int32_t> prev_role(cfg.n_servers, 0);
-        for (uint32_t i = 0; i < res.trace_len; i++) {
-            int32_t a, s, w;
-            int nints = rmc_trace_state(ctx, i, buf.data(), buf.size(), &a, &s, &w);
-            if (nints < 0) break;
-            if (a < 0) std::printf("State %u: <Initial predicate>\n", i + 1);
-            else {
-                const int an = (a == 12 && s >= 0 && s < cfg.n_servers) ? 13 + prev_role[s] : a;  // role: 0 F, 1 C, 2 L
-                const Loc &L = locs[an];
-                if (L.l0)
-                    std::printf("State %u: <%s line %d, col %d to line %d, col %d of module %s>\n", i + 1,
-                                names[an].c_str(), L.l0, L.c0, L.l1, L.c1, pm.module.c_str());
-                else
-                    std::printf("State %u: <%s(%s)>\n", i + 1, names[an].c_str(), pm.servers[s].c_str());
-            }
-            for (int q = 0; q < cfg.n_servers; q++) prev_role[q] = buf[2 * cfg.n_servers + q];  // unpacked: vf, ct, role
-            std::printf("%s\n", pr.state(buf.data()).c_str());
-        }
-    }
+    if (res.status == RMC_DONE) std::printf("Model checking completed. No error has been found.\n");
+    else exit_code = print_error(ctx, cfg, res.status, res.violated, res.trace_len);
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::printf("%llu states generated, %llu distinct states found, %llu states left on queue.\n",
                 (unsigned long long)res.generated, (unsigned long long)res.distinct, (unsigned long long)res.queue);
@@ -647,8 +687,51 @@ int main(int argc, char **argv) {
     phase_time("destroyed");
     return exit_code;
     };
+    // -simulate: seeded random behaviours (rmc_simulate) instead of the search
+    auto sim = [&](const rmc_config &cfg) -> int {
+        const auto t0 = std::chrono::steady_clock::now();
+        void *ctx = nullptr;
+        int rc = rmc_create(&cfg, &ctx);
+        if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d)\n", rc); return 75; }
+        rmc_sim_config sc{};
+        sc.num_walks = sim_num;
+        sc.seed = sim_seed;
+        sc.depth = (uint32_t)sim_depth;
+        rmc_sim_result sr{};
+        rc = rmc_simulate(ctx, &sc, &sr, nullptr, nullptr);
+        if (rc < 0) {
+            std::printf("Error: %s\n", rmc_last_error(ctx));
+            rmc_destroy(ctx);
+            return 75;
+        }
+        int exit_code = 0;
+        if (sr.status == RMC_DONE) {
+            std::printf("Simulation completed. No error has been found.\n");
+        } else {
+            uint32_t tl = 0;
+            rmc_trace_len(ctx, &tl);
+            exit_code = print_error(ctx, cfg, sr.status, sr.violated, tl);
+            std::printf("The error is in behaviour %llu (%u states) of seed %llu.\n", (unsigned long long)sr.err_walk,
+                        sr.err_len, sim_seed);
+        }
+        const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::printf("Simulation using seed %llu: %llu behaviours checked (longest %u states, %llu ended in a state "
+                    "without successors).\n", sim_seed, (unsigned long long)sr.walks, sr.longest,
+                    (unsigned long long)sr.ended_early);
+        std::printf("%llu states checked, %llu states generated.\n", (unsigned long long)sr.states,
+                    (unsigned long long)sr.generated);
+        std::printf("Finished in %.2fs at (%s)\n", el, now_str().c_str());
+        std::printf("GPU: %.0f walk steps/s over %.3f s of walks (MI355X).\n",
+                    sr.seconds > 0 ? sr.states / sr.seconds : 0.0, sr.seconds);
+        std::fflush(stdout);
+        std::fflush(stderr);
+        rmc_destroy(ctx);
+        return exit_code;
+    };
     if (gpus > 1 || onerank) return run_ranks(gpus, onerank, cfg, check);
+    const std::function<int(const rmc_config &)> body = simulate ? std::function<int(const rmc_config &)>(sim)
+                                                                 : std::function<int(const rmc_config &)>(check);
     const char *det = std::getenv("RMC_DETACH");  // RMC_DETACH=0: one process, exit after the teardown
-    if (det && std::string(det) == "0") return check(cfg);
-    return run_detached(cfg, check);
+    if (det && std::string(det) == "0") return body(cfg);
+    return run_detached(cfg, body);
 }

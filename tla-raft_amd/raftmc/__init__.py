@@ -79,6 +79,20 @@ class _Result(ctypes.Structure):
     ]
 
 
+class _SimConfig(ctypes.Structure):
+    _fields_ = [("num_walks", ctypes.c_uint64), ("seed", ctypes.c_uint64), ("depth", ctypes.c_uint32),
+                ("batch_walks", ctypes.c_uint32)]
+
+
+class _SimResult(ctypes.Structure):
+    _fields_ = [
+        ("status", ctypes.c_int32), ("violated", ctypes.c_int32), ("walks", ctypes.c_uint64),
+        ("states", ctypes.c_uint64), ("generated", ctypes.c_uint64), ("err_walk", ctypes.c_uint64),
+        ("err_len", ctypes.c_uint32), ("longest", ctypes.c_uint32), ("ended_early", ctypes.c_uint64),
+        ("seconds", ctypes.c_double),
+    ]
+
+
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 _ALLREDUCE = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, _U64P, ctypes.c_int32, ctypes.c_int32)
 _ALLGATHER = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, _U64P, ctypes.c_int32, _U64P)
@@ -136,6 +150,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.rmc_state_path.argtypes = [vp, u64, P(u32), P(u64), u32, P(u32)]
     lib.rmc_fingerprints.argtypes = [vp, P(i32), ctypes.c_size_t, u64, P(u64)]
     lib.rmc_seen_contains.argtypes = [vp, P(u64), u64, P(ctypes.c_uint8)]
+    lib.rmc_simulate.argtypes = [vp, P(_SimConfig), P(_SimResult), P(u32), P(u32)]
     _lib = lib
     return lib
 
@@ -199,6 +214,27 @@ class ModelConfig:
             self._idbuf = ctypes.create_string_buffer(bytes(self.comm_unique_id), 128)
             c.comm_unique_id = ctypes.cast(self._idbuf, ctypes.c_void_p)
         return c
+
+
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def sim_random(seed: int, walk: int, step: int) -> int:
+    """The 32-bit value r of simulation mode's choice (include/rmc.h): this project's own definition,
+    not TLC's random generator."""
+    z = (seed & _M64) ^ ((walk * _GOLDEN) & _M64)
+    z = (z + (step + 1) * _GOLDEN) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    return z >> 32
+
+
+def sim_choice(seed: int, walk: int, step: int, count: int) -> int:
+    """Index of the successor that walk `walk` takes at step `step` (0 = from Init) among `count`
+    successors in TLC order: (r * count) >> 32."""
+    return (sim_random(seed, walk, step) * count) >> 32
 
 
 def probe_peak(device: int = -1, table_log2: int = 28, probes: int = 1 << 28) -> float:
@@ -468,6 +504,23 @@ class Result:
     frontier_peak_bytes: int = 0
 
 
+@dataclass
+class SimResult:
+    """ModelChecker.simulate: the accounted walks (0..err_walk on an error, all of them otherwise)."""
+    status: str
+    violated: Optional[str]
+    walks: int
+    states: int
+    generated: int
+    err_walk: Optional[int]
+    err_len: Optional[int]
+    longest: int
+    ended_early: int
+    seconds: float
+    lengths: Optional[List[int]] = None  # keep_walks: states per walk (0: not accounted)
+    keys: Optional[List[List[Tuple[int, int, int]]]] = None  # keep_walks: (server, action, witness) per step
+
+
 class ModelChecker:
     """One GPU model-checking run (TLC's ModelChecker for myrun.sh:3)."""
 
@@ -580,6 +633,29 @@ class ModelChecker:
                       self.levels if isinstance(self.levels, _LazyLevels) else list(self.levels), r.seen_slots,
                       r.seen_slot_bytes, r.frontier_ring_bytes,
                       r.frontier_peak_bytes)
+
+    def simulate(self, num_walks: int, depth: int = 100, seed: int = 0, batch_walks: int = 0,
+                 keep_walks: bool = False) -> SimResult:
+        """TLC's -simulate on the GPU: num_walks seeded random behaviours of at most `depth` states from
+        Init, the invariants checked on every state (include/rmc.h rmc_simulate).  After an error,
+        trace() returns the erring behaviour.  keep_walks: also every walk's length and step keys."""
+        sc = _SimConfig(num_walks, seed & _M64, depth, batch_walks)
+        r = _SimResult()
+        lens = keys = None
+        if keep_walks and num_walks > 0 and depth > 0:
+            lens = (ctypes.c_uint32 * num_walks)()
+            keys = (ctypes.c_uint32 * max(1, num_walks * (depth - 1)))()
+        rc = self._check(self.lib.rmc_simulate(self.h, ctypes.byref(sc), ctypes.byref(r), lens, keys))
+        err = rc != RMC_DONE
+        out = SimResult(STATUS_NAMES.get(rc, str(rc)), INVARIANT_BY_BIT[r.violated] if r.violated >= 0 else None,
+                        r.walks, r.states, r.generated, r.err_walk if err else None, r.err_len if err else None,
+                        r.longest, r.ended_early, r.seconds)
+        if lens is not None:
+            out.lengths = list(lens)
+            d1 = depth - 1
+            out.keys = [[(k >> 24, (k >> 16) & 0xFF, k & 0xFFFF) for k in keys[w * d1:w * d1 + max(n - 1, 0)]]
+                        for w, n in enumerate(out.lengths)]
+        return out
 
     def trace(self) -> List[Tuple[Optional[Tuple[int, int, int]], dict]]:
         n = ctypes.c_uint32()
