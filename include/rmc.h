@@ -305,6 +305,38 @@ typedef struct rmc_sim_result {
 /* Returns the result's status, or a negative RMC_E_* code. */
 int rmc_simulate(void *ctx, const rmc_sim_config *sc, rmc_sim_result *res, uint32_t *lens_out, uint32_t *keys_out);
 
+/* ---- action coverage (TLC's -coverage) -----------------------------------------------------------
+ * Which disjuncts of Next do the work: per action, the successors it generated and the states first
+ * found through it -- what TLC prints at the end of a -coverage run as distinct:generated.  Action ids
+ * are those of rmc_successors' keys: 0..10 BecomeCandidate .. Restart in Next's order, 11
+ * FollowerAppendEntry (never enabled: always 0), 12 BecomeFollower (the tla:420 variant only).
+ *   generated[a]  successors of action a among those "states generated" counts: self-loops and
+ *                 duplicates included.
+ *   distinct[a]   explored states with global id >= 1 whose trace key carries action a (the action of
+ *                 the successor that TLC -workers 1 met first).
+ *   Init          apart, 1:1 (init_generated / init_distinct).
+ * At every level boundary and in every outcome (done, violation, evaluation error, Assert, deadlock)
+ *     1 + sum(generated) == total generated        1 + sum(distinct) == total distinct
+ * so on an error the counts stop where TLC's counters stop: with p the erring parent and the (server,
+ * action) group of the error's key, the parents before p in the level count in full; at p the
+ * sub-action batches up to and including that group for an invariant or evaluation error (TLC adds a
+ * batch before it fingerprints it), only the batches before it for an Assert, none for a deadlock;
+ * distinct covers the global ids below the total.
+ * Off by default, and then nothing is allocated or launched for it.  rmc_set_coverage: after rmc_create
+ * or rmc_reset and before rmc_init (RMC_E_STATE otherwise); rmc_reset zeroes the counts and keeps the
+ * setting.  While it is on, levels run one per host round trip (device_levels has no effect on the
+ * results), every shard layout counts (levels expanded replicated are counted once, ranks are summed in
+ * the rounds' all-reduces: rmc_get_coverage is local and returns the global totals on every rank), and
+ * rmc_simulate neither reads nor changes the counts.  Checkpoints do not carry them: rmc_resume on a
+ * context with coverage on returns RMC_E_ARG.  rmc_get_coverage: after rmc_init, between steps or after
+ * the run (the counts of the levels finished so far); RMC_E_STATE while coverage is off. */
+typedef struct rmc_coverage {
+    uint64_t generated[16], distinct[16];
+    uint64_t init_generated, init_distinct;
+} rmc_coverage;
+int rmc_set_coverage(void *ctx, int on);
+int rmc_get_coverage(void *ctx, rmc_coverage *out);
+
 /* Measurement support (bench.py): the random-probe peak of the seen-set layout -- `probes`
  * one-slot reads of 16-B slots at uniformly random indices of a 2^table_log2-slot table,
  * best of 3 timed launches; no model-checking state is touched. */

@@ -466,6 +466,10 @@ struct Shard {
     // errors, summary
     unsigned long long *err = nullptr, *sum = nullptr, *hsum = nullptr;
     uint32_t *flags = nullptr;
+    // action coverage (rmc_set_coverage; allocated by the first rmc_init with it on): the level's counts
+    // [0 .. COV_N) and the current chunk's or round's [COV_N .. 2 COV_N), each generated[16] then
+    // distinct[16] by action id; hcov: the pinned copy a level's end, a round or an error stop reads
+    unsigned long long *cov = nullptr, *hcov = nullptr;
     // single GPU with chunk look-ahead: the second staging set (score, hctx, cnt, pnm, hcnt, hoff, err,
     // sum, flags above are the first) and the events of the look-ahead expansion that filled the
     // set the members above point to (Staging; swap_staging keeps both together)
@@ -548,6 +552,44 @@ struct rmc_ctx {
     bool trace_from_sim = false;  // `trace` holds rmc_simulate's erring behaviour, not a run's counterexample
     unsigned long long *d_red = nullptr, *h_red = nullptr;  // collective scratch (RED_CAP values)
     static constexpr int RED_CAP = 64 * (2 * 64 + 8) + (2 * 64 + 8);  // a W x K gathered count matrix + one row
+
+    // ---- action coverage (rmc_set_coverage / rmc_get_coverage; TLC's -coverage) -----------------
+    // Off by default: nothing below is allocated or launched.  On, every chunk of a single-GPU level and
+    // every shard's block of a sharded round is counted twice on the side of the search: k_cover
+    // re-evaluates the chunk's parents and adds the successors each action generates, k_cover_new adds
+    // the actions of the chunk's new states from their trace keys (a sharded round: from its winners'
+    // sidecars, on the shard that found them).  A chunk's counts join its level's (on the device; a
+    // sharded round's ride on the round's all-reduce) once the chunk finished without an error, and a
+    // level's join the run's totals once the level did, so the totals always stand at a level boundary.
+    // At an error the erring chunk is counted again with TLC's cut (error_counts): the generated counts
+    // up to the error's sub-action batch, the distinct ones up to total_distinct.  Levels run one per
+    // host round trip while coverage is on (batch_ok): the device-driven loop reuses a level's ring space
+    // before the host could count it.
+    static constexpr int COV_N = 32;  // generated[16], distinct[16]
+    bool coverage = false;
+    uint64_t cov_total[COV_N] = {0};  // the run's totals without Init, global on every rank
+    uint64_t cov_level[COV_N] = {0};  // sharded: the current level's rounds so far
+    void cov_alloc() {
+        for (Shard &s : sh) {
+            if (s.cov) continue;
+            s.cov = dmalloc<unsigned long long>(2 * COV_N);
+            HIPCHK(hipHostMalloc((void **)&s.hcov, COV_N * 8, hipHostMallocDefault));
+        }
+    }
+    // the parents [p0, p1) of the shard's current level into its chunk counters; pos0 = p0's position in
+    // the level, (bound_pos, slot, kind) = the error to stop at (cov_gen_all: none)
+    void cov_gen(Shard &s, uint64_t p0, uint64_t p1, uint64_t pos0, uint64_t bound_pos, uint32_t slot, int kind) {
+        KParams Q = chunk_params(s);
+        Q.p_begin = p0;
+        Q.p_end = p1;
+        ks.cover(Q, CoverParams{s.cov + COV_N, pos0, bound_pos, slot >> 7, (uint32_t)kind}, stream);
+    }
+    void cov_gen_all(Shard &s, uint64_t p0, uint64_t p1, uint64_t pos0) { cov_gen(s, p0, p1, pos0, ~0ull, 0u, 0); }
+    void cov_chunk_clear(Shard &s) { HIPCHK(hipMemsetAsync(s.cov + COV_N, 0, COV_N * 8, stream)); }
+    // (after the stream was waited for)
+    void cov_add(uint64_t *dst, const unsigned long long *src) const {
+        for (int k = 0; k < COV_N; k++) dst[k] += src[k];
+    }
 
     // progress
     bool inited = false, finished = false;
@@ -1164,7 +1206,9 @@ struct rmc_ctx {
         s.ocnt = nullptr;  // (inside sum)
         dfree(s.OT); dfree(s.ob); dfree(s.ib); dfree(s.oside); dfree(s.iside); dfree(s.ooff);
         dfree(s.isz); dfree(s.ioff);
-        dfree(s.err); dfree(s.sum); dfree(s.flags);
+        dfree(s.err); dfree(s.sum); dfree(s.flags); dfree(s.cov);
+        if (s.hcov) (void)hipHostFree(s.hcov);
+        s.hcov = nullptr;
         dfree(s.score); dfree(s.wcnt); dfree(s.wacc); dfree(s.pnm); dfree(s.hcnt); dfree(s.hoff); dfree(s.wposw); dfree(s.ctick);
         dfree(s.bw); dfree(s.bg); dfree(s.boff); dfree(s.bww); dfree(s.boffw); dfree(s.tickets);
         dfree(s.bn); dfree(s.boffn); dfree(s.plist); dfree(s.hctx);
@@ -1760,6 +1804,7 @@ struct rmc_ctx {
     // ---- BFS --------------------------------------------------------------------------
     int init(rmc_level_stats *st) {
         if (inited) throw Fail(RMC_E_STATE, "rmc_init called twice");
+        if (coverage) cov_alloc();
         auto t0 = std::chrono::steady_clock::now();
         std::vector<uint32_t> rec = init_record();
         const uint32_t rw = record_words(rec.data());
@@ -2067,6 +2112,7 @@ struct rmc_ctx {
         uint64_t level_gen = 0, level_self = 0, level_hfp = 0, level_drop = 0;
         s.nxt_n = 0;
         s.nxt_words = 0;
+        if (coverage) HIPCHK(hipMemsetAsync(s.cov, 0, 2 * COV_N * 8, stream));
         const uint64_t MSW = (uint64_t)ks.maxsucc * (uint64_t)ks.RECW_MAX;
         // Within the level, split chunk k + 1 is expanded on the expansion stream into the other
         // staging set while chunk k probes, counts and commits on the main stream and the host
@@ -2193,6 +2239,9 @@ struct rmc_ctx {
             // the compute units' slots first.  With the expansion first an exhaustion of Raft.cfg
             // measured 3 % faster than the single-stream order, with the probe first 6 % slower
             look_ahead();
+            // coverage: the chunk's generated counts, while its records are whole (its commit writes the
+            // ring only before them)
+            if (coverage) cov_gen_all(s, p0, p1, p0);
             if (split) timed(PH_OTHER, [&] { ks.hash_probe(params(), np_, stream); });
             timed(PH_DEDUP, [&] {
                 ks.wincount(params(), np_, stream);
@@ -2244,6 +2293,11 @@ struct rmc_ctx {
                 seconds += st->seconds;
                 return status;
             }
+            if (coverage) {  // the chunk's new states by action (their trace entries, before the next chunk's
+                             // commit starts the buffer over), then the chunk into the level
+                launch_cover_new(s.pslot + (gid_nxt + s.nxt_n - s.tdev), 1, Wn, s.cov + COV_N + 16, stream);
+                launch_cover_fold(s.cov, s.cov + COV_N, COV_N, stream);
+            }
             s.nxt_n += Wn;
             s.nxt_words += Ww;
             s.peak_words = std::max(s.peak_words, s.cur_words - consumed + s.nxt_words);
@@ -2265,7 +2319,9 @@ struct rmc_ctx {
             status = RMC_DONE;
             queue_at_end = 0;
         }
+        if (coverage) HIPCHK(hipMemcpyAsync(s.hcov, s.cov, COV_N * 8, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));  // the trace copies of the level
+        if (coverage) cov_add(cov_total, s.hcov);
         st->total_generated = total_generated;
         st->total_distinct = total_distinct;
         st->queue = s.cur_n;
@@ -2299,7 +2355,7 @@ struct rmc_ctx {
     bool batch_ok() const {
         const Shard &s = sh[0];
         const uint64_t first = s.cur_n * (uint64_t)ks.maxsucc;
-        return (!multi || (replicated && s.cur_n < shard_min)) && inited && !finished && cfg.device_levels != 1 &&
+        return !coverage && (!multi || (replicated && s.cur_n < shard_min)) && inited && !finished && cfg.device_levels != 1 &&
                s.cur_n > 0 && s.cur_n <= dev_parents() && ring_room(s, first * (uint64_t)ks.RECW_MAX, 0) &&
                seen_room(s, s.T_count + 2 * first);
     }
@@ -2577,6 +2633,18 @@ struct rmc_ctx {
         const int which = (int)(ek & 0xFF);
         const ErrCounts ec = error_counts(s, kind, ek, p0, false);
         const uint64_t gen = gen_before_chunk + ec.gen, winners_before = ec.win;
+        if (coverage) {
+            // the erring chunk again, with TLC's cut: the level's earlier chunks are in the level's counters
+            const bool inv = kind == ERR_INV || kind == ERR_EVAL;
+            cov_chunk_clear(s);
+            cov_gen(s, p0, p + 1, p0, p, (uint32_t)((ek >> 8) & 0xFFFF), kind);
+            launch_cover_new(s.pslot + (gid_nxt + nxt_before - s.tdev), 1, winners_before + (inv ? 1 : 0),
+                             s.cov + COV_N + 16, stream);
+            launch_cover_fold(s.cov, s.cov + COV_N, COV_N, stream);
+            HIPCHK(hipMemcpyAsync(s.hcov, s.cov, COV_N * 8, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            cov_add(cov_total, s.hcov);
+        }
         if (kind == ERR_INV || kind == ERR_EVAL) {
             err_ref = gid_nxt + nxt_before + winners_before;
             total_distinct += nxt_before + winners_before + 1;
@@ -2695,6 +2763,7 @@ struct rmc_ctx {
         const uint64_t B = chunk_parents, MS = (uint64_t)ks.maxsucc;
         uint64_t Fg = 0;
         for (Shard &s : sh) { Fg += s.cur_n; s.nxt_n = 0; s.nxt_words = 0; }
+        if (coverage) std::memset(cov_level, 0, sizeof cov_level);
         allreduce(&Fg, 1, false);
         {
             uint64_t pend = (uint64_t)(-pending_fail);
@@ -2762,7 +2831,10 @@ struct rmc_ctx {
                 // (before any skip: a shard with no parents this round receives items, and they must
                 // not bid in E under an earlier round's tag)
                 s.lx_bid = false;
+                if (coverage) cov_chunk_clear(s);
                 if (!s.np || fail[li]) continue;
+                // coverage: the block's generated counts (position in the level: its global block's)
+                if (coverage) cov_gen_all(s, s.p0, s.p0 + s.np, s.gblk);
                 const bool split = split_min && s.np >= split_min;
                 // (the fused election table holds a round's successors at load <= 1/2: ensure_chunk)
                 s.lx_bid = owner_lxy && split && s.E && s.lcap >= 2 * s.np * MS;
@@ -2918,7 +2990,8 @@ struct rmc_ctx {
                     if (Q.plist) launch_nzlist(Q, s.np, stream);
                 });
             }
-            std::vector<uint64_t> tab((size_t)TAB * W, 0);
+            // (coverage: COV_N more values per shard behind the table, summed by the same all-reduce)
+            std::vector<uint64_t> tab((size_t)(TAB + (coverage ? COV_N : 0)) * W, 0);
             std::vector<uint64_t> ins(NL, 0), wnum(NL, 0), wwords(NL, 0);
             for (size_t li = 0; li < NL; li++) {
                 Shard &s = sh[li];
@@ -2959,9 +3032,14 @@ struct rmc_ctx {
                 Shard &s = sh[li];
                 s.T_count += ins[li];
                 if (!s.np || fail[li]) continue;
+                if (coverage) {  // the round's winners of this shard by action, from their sidecars (.z: the slot key)
+                    launch_cover_new(reinterpret_cast<const uint16_t *>(s.oside) + 4, 8, wnum[li], s.cov + COV_N + 16, stream);
+                    HIPCHK(hipMemcpyAsync(s.hcov, s.cov + COV_N, COV_N * 8, hipMemcpyDeviceToHost, stream));
+                }
                 HIPCHK(hipMemcpyAsync(s.hsum, s.sum, (SUM_INS_COMMIT + 1) * 8, hipMemcpyDeviceToHost, stream));
                 HIPCHK(hipStreamSynchronize(stream));
                 HIPCHK(hipGetLastError());
+                if (coverage) cov_add(&tab[(size_t)TAB * W + (size_t)COV_N * s.id], s.hcov);
                 ins[li] += s.hsum[SUM_INS_COMMIT];  // (a split round's own winners, inserted by its commit)
                 s.T_count += s.hsum[SUM_INS_COMMIT];
                 if (s.hsum[2 + ERR_NSLOTS] && !fail[li]) {
@@ -2982,7 +3060,7 @@ struct rmc_ctx {
             }
             collect_times(st);
             for (size_t li = 0; li < NL; li++) tab[TAB * sh[li].id + 6] = (uint64_t)(-fail[li]);
-            allreduce(tab.data(), TAB * W, false);  // rows: each shard's own, zero elsewhere
+            allreduce(tab.data(), (int)tab.size(), false);  // rows: each shard's own, zero elsewhere
             {
                 uint64_t worst = 0;
                 for (int t = 0; t < W; t++) worst = std::max(worst, tab[TAB * t + 6]);
@@ -3000,6 +3078,9 @@ struct rmc_ctx {
                 seconds += st->seconds;
                 return status;
             }
+            if (coverage)
+                for (int t = 0; t < W; t++)
+                    for (int k = 0; k < COV_N; k++) cov_level[k] += tab[(size_t)TAB * W + (size_t)COV_N * t + k];
             // (7) winners to the shards owning their global next-level indices (rmc_plan.h route_pieces)
             std::vector<uint64_t> A(W + 1, level_new);
             for (int t = 0; t < W; t++) A[t + 1] = A[t] + tab[TAB * t + 1];
@@ -3190,6 +3271,8 @@ struct rmc_ctx {
         collect_times(st);
         total_generated += level_gen;
         total_distinct += level_new;
+        if (coverage)
+            for (int k = 0; k < COV_N; k++) cov_total[k] += cov_level[k];
         st->generated = level_gen;
         st->new_states = level_new;
         st->new_bytes = level_words * 4;
@@ -3225,7 +3308,7 @@ struct rmc_ctx {
                       uint64_t level_new, uint64_t Fg, uint64_t gbase, rmc_level_stats *st) {
         const uint64_t g = gk >> 24;
         const uint32_t slot = (uint32_t)((gk >> 8) & 0xFFFF);
-        uint64_t loc[2] = {0, 0};
+        uint64_t loc[2 + COV_N] = {0};
         for (Shard &s : sh)
             if (s.id == e) {
                 const uint64_t p = s.p0 + (g - s.gblk);
@@ -3235,8 +3318,23 @@ struct rmc_ctx {
                 const ErrCounts ec = error_counts(s, kind, ek, s.p0, true);
                 loc[0] = ec.gen;
                 loc[1] = ec.win;
+                if (coverage) {  // the erring block again, with TLC's cut; its winners up to the error
+                    const bool inv = kind == ERR_INV || kind == ERR_EVAL;
+                    cov_chunk_clear(s);
+                    cov_gen(s, s.p0, p + 1, s.gblk, g, slot, kind);
+                    launch_cover_new(reinterpret_cast<const uint16_t *>(s.oside) + 4, 8, ec.win + (inv ? 1 : 0),
+                                     s.cov + COV_N + 16, stream);
+                    HIPCHK(hipMemcpyAsync(s.hcov, s.cov + COV_N, COV_N * 8, hipMemcpyDeviceToHost, stream));
+                    HIPCHK(hipStreamSynchronize(stream));
+                    cov_add(loc + 2, s.hcov);
+                }
             }
-        allreduce(loc, 2, false);
+        allreduce(loc, coverage ? 2 + COV_N : 2, false);
+        if (coverage)  // every earlier round, the round's shards before e, e's share
+            for (int k = 0; k < COV_N; k++) {
+                cov_total[k] += cov_level[k] + loc[2 + k];
+                for (int t = 0; t < e; t++) cov_total[k] += tab[(size_t)TAB * W + (size_t)COV_N * t + k];
+            }
         uint64_t gen = level_gen + loc[0], winb = level_new + loc[1];
         for (int t = 0; t < e; t++) {
             gen += tab[TAB * t + 0];
@@ -3648,6 +3746,8 @@ struct rmc_ctx {
     // (or takes another resume) as if the failed call had not been made.
     void resume(const char *path_arg) {
         if (inited) throw Fail(RMC_E_STATE, "resume: needs a context not yet initialised (rmc_create or rmc_reset)");
+        if (coverage)
+            throw Fail(RMC_E_ARG, "resume: checkpoints do not carry action coverage (rmc_set_coverage is on)");
         try {
             resume_body(path_arg);
         } catch (...) {
@@ -3856,6 +3956,8 @@ struct rmc_ctx {
         status = RMC_OK;
         depth = 0;
         total_generated = total_distinct = queue_at_end = 0;
+        std::memset(cov_total, 0, sizeof cov_total);  // (the setting stays)
+        std::memset(cov_level, 0, sizeof cov_level);
         violated = -1;
         err_ref = 0;
         err_last_slot = KEY_NONE;
@@ -4000,6 +4102,31 @@ int rmc_set_timing(void *ctx, uint32_t phases) {
     return guarded(c, [&] {
         c->timing_on = phases != 0;
         if (phases != 0) c->cfg.timing_phases = phases == 0xFFFFFFFFu ? 0u : phases;
+        return RMC_OK;
+    });
+}
+
+int rmc_set_coverage(void *ctx, int on) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        if (c->inited) throw Fail(RMC_E_STATE, "rmc_set_coverage: after rmc_create or rmc_reset, before rmc_init");
+        c->coverage = on != 0;
+        return RMC_OK;
+    });
+}
+
+int rmc_get_coverage(void *ctx, rmc_coverage *out) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    if (!out) return RMC_E_ARG;
+    return guarded(c, [&] {
+        if (!c->coverage) throw Fail(RMC_E_STATE, "rmc_get_coverage: coverage is off (rmc_set_coverage)");
+        if (!c->inited) throw Fail(RMC_E_STATE, "rmc_get_coverage before rmc_init");
+        std::memset(out, 0, sizeof *out);
+        for (int k = 0; k < 16; k++) {
+            out->generated[k] = c->cov_total[k];
+            out->distinct[k] = c->cov_total[16 + k];
+        }
+        out->init_generated = out->init_distinct = 1;
         return RMC_OK;
     });
 }

@@ -240,6 +240,19 @@ RMC_HD uint32_t walk_choice(uint64_t seed, uint64_t walk, uint32_t step, uint32_
     return (uint32_t)(((mix64(z) >> 32) * (uint64_t)c) >> 32);
 }
 
+// Action coverage (rmc_set_coverage; TLC's -coverage): k_cover adds, per action id (rmc_spec.h Act), the
+// successors generated by the parents [P.p_begin, P.p_end) of a launch to gen[0 .. COV_ACTS).  pos0 is the
+// position in the level of parent P.p_begin (a sharded round: its block's global position), and the bound
+// is where TLC's counter stops at an error: the parent at level position bound_pos counts up to (an
+// invariant or evaluation error: and including) the sub-action batch bound_grp = error key >> 7, a
+// deadlocked one not at all, later parents not at all.  bound_pos all ones: no bound.
+constexpr int COV_ACTS = 13;     // BecomeCandidate .. Restart, FollowerAppendEntry (never enabled), BecomeFollower
+struct CoverParams {
+    unsigned long long *gen;
+    uint64_t pos0, bound_pos;
+    uint32_t bound_grp, bound_kind;  // ErrSlot
+};
+
 struct KernelSet {
     int N, V, MR, MCAP, CCW, RECW_MAX, maxsucc;
     int ctxw;                                                 // hash-context words per parent (split chunks)
@@ -261,6 +274,7 @@ struct KernelSet {
     void (*local_flags)(const KParams &, uint64_t np, Seen, const ESlot *OT, uint32_t round, uint32_t W,
                         uint32_t self, uint64_t g0, unsigned long long *inserted, hipStream_t);
     void (*walk)(const KParams &, const WalkParams &, hipStream_t);  // simulation: one batch of random walks
+    void (*cover)(const KParams &, const CoverParams &, hipStream_t);  // coverage: successors generated per action
     void (*fp_states)(const KParams &, uint64_t n, hipStream_t);  // fp of front[0..n) -> fp
     void (*inv_states)(const KParams &, uint64_t n, int32_t *out, hipStream_t); // per state: 1/0/-1 for inv_mask bits
     // host codec of the packed core (rmc_spec.h Codec)
@@ -308,6 +322,10 @@ void launch_side_sizes(const uint4 *side, uint64_t n, uint32_t *sz, hipStream_t 
 void launch_accept_side(const uint4 *side, const uint32_t *off, uint64_t n, uint64_t rel0, uint64_t *noff,
                         uint64_t *par, uint16_t *pslot, hipStream_t s);
 void launch_owner_of(const ulonglong2 *fp, uint32_t W, uint32_t *out, hipStream_t s);
+// coverage: dist[key_action(keys[i * stride])] += 1 for i < n
+void launch_cover_new(const uint16_t *keys, uint32_t stride, uint64_t n, unsigned long long *dist, hipStream_t s);
+// ... dst[i] += src[i], src[i] = 0 for i < n <= 64 (a chunk's counters into its level's)
+void launch_cover_fold(unsigned long long *dst, unsigned long long *src, int n, hipStream_t s);
 // out[i] = 1 if fp[i] is in `seen` -- for the fingerprints the shard `self` of W owns (W = 1: all)
 void launch_seen_query(const ulonglong2 *fp, uint64_t n, Seen seen, uint32_t W, uint32_t self, uint8_t *out,
                        hipStream_t s);

@@ -3938,6 +3938,79 @@ __global__ __launch_bounds__(64) void k_walk(KParams P, WalkParams Wp) {
     }
 }
 
+// ---- action coverage (rmc_set_coverage; TLC's -coverage) -------------------------------------------
+// The successors each action of Next generates, counted on the side of the BFS: a 64-lane wave per
+// parent, grid-strided over the chunk's frontier records.  A parent is loaded and its candidates are
+// evaluated exactly as k_expand and k_walk do -- and that is all: no ranks, no records, no fingerprints,
+// no seen set.  What TLC's "states generated" counts is every enabled candidate, self-loops and repeats
+// included, so per action the wave adds the popcount of the ballot of lanes whose candidate is enabled
+// and carries that action in its slot key.  The counters are wave-uniform and stay in registers across
+// the wave's parents; the wave adds them to Cp.gen once, at its end (64-bit integer atomics: the sums
+// are the same under every schedule).
+// The bound stops the count where TLC's counter stops at an error (the engine's error_counts): the
+// parents at level positions below bound_pos count in full, the parent at bound_pos up to and including
+// the (server, action) batch bound_grp of an invariant or evaluation error, only the batches before it
+// for an Assert, nothing for a deadlock; later parents do not count.
+template <int N, int V, int MR, bool BFV>
+__global__ __launch_bounds__(64) void k_cover(KParams P, CoverParams Cp) {
+    using Lo = Layout<N, V>;
+    constexpr int NC = MR + 1 + (BFV ? MR : 0);  // candidates per lane: messages, slot, BecomeFollower
+    __shared__ uint32_t pcore[Lo::NW + N];
+    extern __shared__ uint32_t sBM[];            // bitmap of the parent's message ids (P.t.bmw words)
+    if (!level_args(P)) return;
+    const int lane = threadIdx.x;
+    uint64_t acc[COV_ACTS];
+#pragma unroll
+    for (int a = 0; a < COV_ACTS; a++) acc[a] = 0;
+    for (uint64_t p = P.p_begin + blockIdx.x; p < P.p_end; p += gridDim.x) {
+        const uint64_t pos = Cp.pos0 + (p - P.p_begin);
+        if (pos > Cp.bound_pos) break;  // (the wave's later parents lie further on still)
+        uint32_t lim = 0xFFFFFFFFu;     // the key groups (server, action) below it count
+        if (pos == Cp.bound_pos) {
+            if (Cp.bound_kind == ERR_DEADLOCK) break;
+            lim = Cp.bound_kind == ERR_ASSERT ? Cp.bound_grp : Cp.bound_grp + 1u;
+        }
+        Wave<N, V, MR> W;
+        load_parent<N, V, MR, false>(P, rec_start<Spec<N, V, MR>::RECW_MAX>(P, p), lane, W, nullptr, nullptr, pcore);
+        msg_bitmap<N, V, MR>(sBM, P.t.bmw, W, lane);
+        W.bm = sBM;
+        Succ<N, V, MR> cand[NC];
+        uint32_t akey = KEY_NONE;
+        int ln = lane;  // (opaque, as in k_expand: what the evaluation derives from it is not hoisted)
+        asm volatile("" : "+v"(ln));
+        uint32_t mid[MR], sid[N - 1];
+        {
+            uint32_t snat[N - 1];
+            slot_nats<N, V, MR>(P, W, ln, snat);
+#pragma unroll
+            for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
+#pragma unroll
+            for (int q = 0; q < N - 1; q++) sid[q] = nat_lookup(P, snat[q]);
+        }
+#pragma unroll
+        for (int r = 0; r < MR; r++)
+            eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey, nullptr, mid[r]);
+        eval_slot<N, V, MR>(P, W, ln, cand[MR], nullptr, sid);
+#pragma unroll
+        for (int r = 0; r < NC; r++) {
+            const uint32_t k = cand[r].key;
+            const bool on = k != KEY_NONE && (k >> 7) < lim;
+            const uint32_t act = key_action(k);
+#pragma unroll
+            for (int a = 0; a < COV_ACTS; a++) {
+                if (a == (int)FAPP) continue;  // never enabled
+                acc[a] += (uint64_t)__popcll(__ballot(on && act == (uint32_t)a));
+            }
+        }
+        __syncthreads();  // the bitmap and the core in LDS are read out before the next parent's go in
+    }
+    uint64_t mine = 0;
+#pragma unroll
+    for (int a = 0; a < COV_ACTS; a++)
+        if (lane == a) mine = acc[a];
+    if (lane < COV_ACTS && mine) atomicAdd(&Cp.gen[lane], (unsigned long long)mine);
+}
+
 static inline unsigned grid_for(uint64_t n) {
     const uint64_t cap = 256ull * RMC_GRID_PER_CU;  // one-wave blocks per CU (default 32) on 256 CUs
     return (unsigned)(n < cap ? (n ? n : 1) : cap);
@@ -4028,6 +4101,9 @@ struct Launch {
     static void walk(const KParams &P, const WalkParams &wp, hipStream_t s) {
         hipLaunchKernelGGL((k_walk<N, V, MR, BFV>), dim3(grid_for(wp.n)), dim3(64), bm_bytes(P), s, P, wp);
     }
+    static void cover(const KParams &P, const CoverParams &cp, hipStream_t s) {
+        hipLaunchKernelGGL((k_cover<N, V, MR, BFV>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64), bm_bytes(P), s, P, cp);
+    }
     static void fps(const KParams &P, uint64_t n, hipStream_t s) {
         hipLaunchKernelGGL((k_fp_states<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n);
     }
@@ -4055,6 +4131,7 @@ static void fill(KernelSet *ks) {
     ks->local_elect = &Launch<N, V, MR, BFV>::local_elect;
     ks->local_flags = &Launch<N, V, MR, BFV>::local_flags;
     ks->walk = &Launch<N, V, MR, BFV>::walk;
+    ks->cover = &Launch<N, V, MR, BFV>::cover;
     ks->fp_states = &Launch<N, V, MR>::fps;
     ks->inv_states = &Launch<N, V, MR>::invs;
     ks->encode = &Launch<N, V, MR>::enc;
@@ -4275,6 +4352,45 @@ __global__ __launch_bounds__(256) void k_accept_side(const uint4 *__restrict__ s
         par[i] = (uint64_t)e.x | ((uint64_t)e.y << 32);
         pslot[i] = (uint16_t)e.z;
     }
+}
+
+// Action coverage: the histogram of the actions that found n new states, from their slot keys (a trace
+// buffer's pslot, stride 1; a sharded round's winner sidecars, the low half of .z, stride 8).  A lane
+// per entry; a wave counts an action's entries with one ballot, a block gathers its waves in LDS and
+// adds each action it met to dist once.
+__global__ __launch_bounds__(256) void k_cover_new(const uint16_t *__restrict__ keys, uint32_t stride, uint64_t n,
+                                                   unsigned long long *dist) {
+    __shared__ uint32_t h[COV_ACTS];
+    if (threadIdx.x < COV_ACTS) h[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    // (every lane of a wave makes the same number of rounds: the ballots see whole waves)
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += step) {
+        const uint64_t i = base + threadIdx.x;
+        const bool on = i < n;
+        const uint32_t act = on ? key_action(keys[i * stride]) : 0u;
+#pragma unroll
+        for (int a = 0; a < COV_ACTS; a++) {
+            const uint32_t c = (uint32_t)__popcll(__ballot(on && act == (uint32_t)a));
+            if (c && (threadIdx.x & 63) == 0) atomicAdd(&h[a], c);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < COV_ACTS && h[threadIdx.x]) atomicAdd(&dist[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+// ... and a chunk's counters into its level's: dst += src, src = 0
+__global__ void k_cover_fold(unsigned long long *dst, unsigned long long *src, int n) {
+    const int i = (int)threadIdx.x;
+    if (i < n) {
+        dst[i] += src[i];
+        src[i] = 0;
+    }
+}
+void launch_cover_fold(unsigned long long *dst, unsigned long long *src, int n, hipStream_t s) {
+    hipLaunchKernelGGL(k_cover_fold, dim3(1), dim3(64), 0, s, dst, src, n);
+}
+void launch_cover_new(const uint16_t *keys, uint32_t stride, uint64_t n, unsigned long long *dist, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_cover_new, dim3(grid256(n)), dim3(256), 0, s, keys, stride, n, dist);
 }
 
 __global__ void k_owner_of(const ulonglong2 *__restrict__ fp, uint32_t W, uint32_t *out) {

@@ -1,6 +1,7 @@
 // raftmc -- TLC-compatible command line over librmc (the drop-in for myrun.sh:3).
 //
 //   raftmc [-deadlock] [-workers N] [-config Raft.cfg] [-device D] [-gpus N] [-msgcap C] [-seenlog2 K] Raft.tla
+//   raftmc -coverage MIN ... Raft.tla   (TLC's -coverage: the per-action distinct:generated report at the end)
 //   raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config Raft.cfg] [-device D] [-msgcap C] Raft.tla
 //
 // Accepts the flags myrun.sh passes to TLC (myrun.sh:3), reads the same Raft.tla /
@@ -84,7 +85,7 @@ std::vector<Loc> action_locations(const std::string &tla, const std::vector<std:
     }
     std::vector<Loc> locs(names.size());
     for (size_t a = 0; a < names.size(); a++) {
-        const std::string head = names[a] + "(s) ==";
+        const std::string head = names[a] == "Init" ? std::string("Init ==") : names[a] + "(s) ==";
         for (size_t i = 0; i < lines.size(); i++) {
             if (lines[i].compare(0, head.size(), head) != 0) continue;
             // body starts at the first non-blank character after "=="
@@ -221,9 +222,11 @@ struct Printer {
 int usage(const char *msg) {
     std::fprintf(stderr, "raftmc: %s\nusage: raftmc [-deadlock] [-workers N] [-config FILE.cfg] [-device D] "
                          "[-gpus N [-onerank] [-shardmin K]] [-msgcap C] [-seenlog2 K] [-checkpoint MIN] [-metadir DIR] "
-                         "[-recover DIR] FILE.tla\n"
+                         "[-recover DIR] [-coverage MIN] FILE.tla\n"
                          "       raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config FILE.cfg] [-device D] "
                          "[-msgcap C] FILE.tla\n"
+                         "  -coverage MIN  per-action coverage (distinct:generated) at the end of the search; the interval "
+                         "is parsed as TLC's, only the final report is printed\n"
                          "  -simulate  random behaviours instead of the breadth-first search; num=N of them (default "
                          "1000000; TLC's default is unbounded)\n"
                          "  -depth D   states per behaviour at most (default 100, as TLC)\n"
@@ -421,6 +424,7 @@ int main(int argc, char **argv) {
     bool simulate = false, ckpt_given = false, seed_given = false, sim_bad = false;  // TLC -simulate [num=N]
     unsigned long long sim_num = 1000000, sim_seed = 0;  // (TLC's -simulate is unbounded without num=)
     long long sim_depth = 100;                           // TLC -depth
+    bool coverage = false, cov_bad = false;              // TLC -coverage <minutes>
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *f) -> const char * {
@@ -446,6 +450,11 @@ int main(int argc, char **argv) {
                 sim_num = digits ? std::strtoull(v.c_str() + 4, &end, 10) : 0;
                 if (!digits || *end || sim_num == 0) sim_bad = true;
             }
+        } else if (a == "-coverage") {
+            coverage = true;
+            char *end = nullptr;
+            if (i + 1 >= argc || !isdigit((unsigned char)argv[i + 1][0])) cov_bad = true;
+            else if (std::strtod(argv[++i], &end), *end) cov_bad = true;
         } else if (a == "-depth") sim_depth = std::atoll(need("-depth"));
         else if (a == "-seed") { sim_seed = (unsigned long long)std::strtoll(need("-seed"), nullptr, 10); seed_given = true; }
         else if (a == "-metadir") metadir = need("-metadir");
@@ -455,6 +464,11 @@ int main(int argc, char **argv) {
         else if (a.size() > 4 && a.compare(a.size() - 4, 4, ".tla") == 0) tla_path = a;
         else if (a[0] != '-' && tla_path.empty()) tla_path = a + ".tla";
         else return usage(("unsupported option " + a).c_str());
+    }
+    if (coverage) {  // refused before anything touches a device
+        if (cov_bad) return usage("-coverage takes a number of minutes");
+        if (simulate) return usage("-coverage cannot be combined with -simulate");
+        if (!recover_dir.empty()) return usage("-coverage cannot be combined with -recover (checkpoints do not carry it)");
     }
     if (simulate) {  // refused before anything touches a device
         if (sim_bad) return usage("-simulate takes num=N with N >= 1");
@@ -583,6 +597,11 @@ int main(int argc, char **argv) {
     phase_time("created");
     if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d)\n", rc); return 75; }
     rmc_level_stats st;
+    if (coverage && rmc_set_coverage(ctx, 1) < 0) {
+        std::printf("Error: %s\n", rmc_last_error(ctx));
+        rmc_destroy(ctx);
+        return 75;
+    }
     if (!recover_dir.empty()) {
         // TLC -recover: carry on from the checkpoint in that directory (rmc_resume)
         const std::string f = recover_dir + "/raftmc.ckpt";
@@ -658,6 +677,33 @@ int main(int argc, char **argv) {
     int exit_code = 0;
     if (res.status == RMC_DONE) std::printf("Model checking completed. No error has been found.\n");
     else exit_code = print_error(ctx, cfg, res.status, res.violated, res.trace_len);
+    rmc_coverage cov;
+    const int cov_rc = coverage && cfg.rank == 0 ? rmc_get_coverage(ctx, &cov) : RMC_OK;
+    if (cov_rc < 0) std::printf("Error: no coverage statistics: %s\n", rmc_last_error(ctx));
+    if (coverage && cfg.rank == 0 && cov_rc == RMC_OK) {
+        // TLC's end-of-run coverage block, one line per disjunct of Next in textual order with the ranges
+        // the trace headers use.  BecomeFollower (tla:420 variant) is one line here; TLC would report its
+        // three disjuncts apart.  FollowerAppendEntry is not in Next.
+        std::vector<std::string> names(kActionNames, kActionNames + 13);
+        names.push_back("Init");
+        const std::vector<Loc> locs = action_locations(tla, names);
+        auto line = [&](int a, unsigned long long d, unsigned long long g) {
+            const Loc &L = locs[a];
+            if (L.l0)
+                std::printf("<%s line %d, col %d to line %d, col %d of module %s>: %llu:%llu\n", names[a].c_str(), L.l0,
+                            L.c0, L.l1, L.c1, pm.module.c_str(), d, g);
+            else
+                std::printf("<%s>: %llu:%llu\n", names[a].c_str(), d, g);
+        };
+        std::printf("The coverage statistics at %s\n", now_str().c_str());
+        line(13, (unsigned long long)cov.init_distinct, (unsigned long long)cov.init_generated);
+        static const int order[12] = {0, 1, 12, 2, 3, 4, 5, 6, 7, 8, 9, 10};  // Next's order; 12 = BecomeFollower
+        for (int a : order) {
+            if (a == 12 && cfg.spec_variant != RMC_SPEC_BECOME_FOLLOWER) continue;
+            line(a, (unsigned long long)cov.distinct[a], (unsigned long long)cov.generated[a]);
+        }
+        std::printf("End of statistics.\n");
+    }
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::printf("%llu states generated, %llu distinct states found, %llu states left on queue.\n",
                 (unsigned long long)res.generated, (unsigned long long)res.distinct, (unsigned long long)res.queue);

@@ -93,6 +93,11 @@ class _SimResult(ctypes.Structure):
     ]
 
 
+class _Coverage(ctypes.Structure):
+    _fields_ = [("generated", ctypes.c_uint64 * 16), ("distinct", ctypes.c_uint64 * 16),
+                ("init_generated", ctypes.c_uint64), ("init_distinct", ctypes.c_uint64)]
+
+
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 _ALLREDUCE = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, _U64P, ctypes.c_int32, ctypes.c_int32)
 _ALLGATHER = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, _U64P, ctypes.c_int32, _U64P)
@@ -151,6 +156,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.rmc_fingerprints.argtypes = [vp, P(i32), ctypes.c_size_t, u64, P(u64)]
     lib.rmc_seen_contains.argtypes = [vp, P(u64), u64, P(ctypes.c_uint8)]
     lib.rmc_simulate.argtypes = [vp, P(_SimConfig), P(_SimResult), P(u32), P(u32)]
+    # (additive within ABI 5: an older library of the same ABI, as an A/B run loads through RMC_LIBRARY,
+    # lacks the two; set_coverage() then raises)
+    if hasattr(lib, "rmc_set_coverage"):
+        lib.rmc_set_coverage.argtypes = [vp, i32]
+        lib.rmc_get_coverage.argtypes = [vp, P(_Coverage)]
     _lib = lib
     return lib
 
@@ -655,6 +665,23 @@ class ModelChecker:
             d1 = depth - 1
             out.keys = [[(k >> 24, (k >> 16) & 0xFF, k & 0xFFFF) for k in keys[w * d1:w * d1 + max(n - 1, 0)]]
                         for w, n in enumerate(out.lengths)]
+        return out
+
+    def set_coverage(self, on: bool = True) -> None:
+        """TLC's -coverage: count, per action of Next, the successors generated and the states first found
+        (include/rmc.h rmc_set_coverage).  On a fresh or reset checker, before init() / run()."""
+        if not hasattr(self.lib, "rmc_set_coverage"):
+            raise RmcError("this librmc.so has no action coverage (rmc_set_coverage): rebuild it")
+        self._check(self.lib.rmc_set_coverage(self.h, 1 if on else 0))
+
+    def coverage(self) -> dict:
+        """{action name: (distinct, generated)} over ACTIONS, plus "Init": the levels finished so far (on an
+        error: up to TLC's counters at the error).  1 + the sums equal the run's distinct / generated."""
+        c = _Coverage()
+        self._check(self.lib.rmc_get_coverage(self.h, ctypes.byref(c)))
+        out = {"Init": (c.init_distinct, c.init_generated)}
+        for a, name in enumerate(ACTIONS):
+            out[name] = (c.distinct[a], c.generated[a])
         return out
 
     def trace(self) -> List[Tuple[Optional[Tuple[int, int, int]], dict]]:
