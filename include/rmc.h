@@ -337,6 +337,50 @@ typedef struct rmc_coverage {
 int rmc_set_coverage(void *ctx, int on);
 int rmc_get_coverage(void *ctx, rmc_coverage *out);
 
+/* Continuation (TLC's -continue): search past invariant violations and count them per invariant.
+ * With it on, a new state on which an invariant evaluates to FALSE no longer ends the search: it is
+ * inserted, enqueued and expanded like any other.  Per new state the invariants are evaluated in cfg
+ * order up to the first FALSE one (TLC's break), so every violating state is attributed to exactly one
+ * invariant, and an invariant listed after a FALSE one is not evaluated on that state (it cannot raise
+ * its evaluation error there).  Init is checked the same way (a violation at Init: first_level 1).
+ * Everything else stops the run as without it -- an invariant's evaluation error, UpdateTerm's Assert,
+ * a deadlock with deadlock checking on, RMC_E_CAPACITY -- with the same precedence, counters, trace and
+ * codes.  A run that exhausts the state space ends with status RMC_DONE and violated = -1, its counters
+ * those of the same configuration without invariants; the violations are reported on the side:
+ *   count[b]        explored states attributed to the invariant with bit index b (RMC_INV_* = 1 << b)
+ *   first_level[b]  level of the first such state in TLC -workers 1 order, i.e. of the smallest global
+ *                   id (1 = Init's level; 0 = none)
+ *   total           sum of count[]
+ * rmc_get_violation_levels: count[b] per BFS level, per_level[0] Init's level, *n levels (the depth
+ * reached so far; RMC_E_ARG if cap is smaller); they sum to count[b].  rmc_violation_trace makes the
+ * behaviour from Init to that invariant's first violating state the current trace of rmc_trace_len /
+ * rmc_trace_state, until the next error, rmc_reset or rmc_simulate; RMC_E_ARG if the invariant has no
+ * violation.  With ranks it walks the distributed trace: every rank calls it.
+ * When another error stops the run, the counts cover exactly the explored states with global id below
+ * the reported `distinct` (the cut rmc_get_coverage's distinct[] uses): a violating state of the erring
+ * level that TLC -workers 1 would not have reached is not counted and cannot be first.  Counts, levels
+ * and first states are the same under every execution path and shard layout.
+ * Off by default, and then nothing is launched for it (one device word behind each set of error slots is all
+ * that is allocated).  rmc_set_continue: after rmc_create
+ * or rmc_reset and before rmc_init (RMC_E_STATE otherwise); rmc_reset zeroes the counts and keeps the
+ * setting.  While it is on each finished level is counted by a pass of its own over its records, inside the
+ * device-driven level loop as well (device_levels has no effect on the results); levels expanded
+ * replicated are counted once, ranks are summed in all-reduces: rmc_get_violations is local and returns
+ * the global totals on every rank.  rmc_simulate neither reads nor changes the counts and stops at its
+ * first error.  It composes with coverage: rmc_get_coverage is then that of the run that did not stop.
+ * Checkpoints do not carry the counts: rmc_resume on a context with continuation on returns RMC_E_ARG.
+ * rmc_get_violations / rmc_get_violation_levels: after rmc_init, between steps or after the run (the
+ * levels finished so far); RMC_E_STATE while continuation is off. */
+typedef struct rmc_violations {
+    uint64_t count[16];        /* by invariant bit index */
+    int32_t  first_level[16];  /* 0 = none */
+    uint64_t total;
+} rmc_violations;
+int rmc_set_continue(void *ctx, int on);
+int rmc_get_violations(void *ctx, rmc_violations *out);
+int rmc_get_violation_levels(void *ctx, uint32_t invariant_bit, uint64_t *per_level, uint32_t cap, uint32_t *n);
+int rmc_violation_trace(void *ctx, uint32_t invariant_bit);
+
 /* Measurement support (bench.py): the random-probe peak of the seen-set layout -- `probes`
  * one-slot reads of 16-B slots at uniformly random indices of a 2^table_log2-slot table,
  * best of 3 timed launches; no model-checking state is touched. */

@@ -470,6 +470,9 @@ struct Shard {
     // [0 .. COV_N) and the current chunk's or round's [COV_N .. 2 COV_N), each generated[16] then
     // distinct[16] by action id; hcov: the pinned copy a level's end, a round or an error stop reads
     unsigned long long *cov = nullptr, *hcov = nullptr;
+    // continuation (rmc_set_continue; allocated by the first rmc_init with it on): the scan's counts by
+    // invariant id [0 .. 16) and the smallest violating level positions [16 .. 32); hviol: the pinned copy
+    unsigned long long *viol = nullptr, *hviol = nullptr;
     // single GPU with chunk look-ahead: the second staging set (score, hctx, cnt, pnm, hcnt, hoff, err,
     // sum, flags above are the first) and the events of the look-ahead expansion that filled the
     // set the members above point to (Staging; swap_staging keeps both together)
@@ -589,6 +592,118 @@ struct rmc_ctx {
     // (after the stream was waited for)
     void cov_add(uint64_t *dst, const unsigned long long *src) const {
         for (int k = 0; k < COV_N; k++) dst[k] += src[k];
+    }
+
+    // ---- continuation (rmc_set_continue / rmc_get_violations; TLC's -continue) -------------------
+    // Off by default: nothing below is allocated or launched.  On, a state whose invariant is FALSE does
+    // not stop the run: the commits leave its ERR_INV key unwritten (err[ERR_NSLOTS]: no atomic on one word
+    // per violating state) and first_error does not read that slot, so the state is inserted,
+    // enqueued and expanded like any other, and every level is counted once it stands in its ring: k_viol_scan
+    // evaluates the invariants on the level's records in cfg order up to the first FALSE one and adds, per
+    // invariant, the count and the smallest level position (a sharded level: every shard its part, summed
+    // and min-ed by two all-reduces).  When another error stops the run, the scan of the unfinished level
+    // takes only the records below the reported `distinct` -- the appended ones, and in a sharded round
+    // the winners still in the outboxes.  The device-driven level loop keeps running: a scan launch
+    // follows each level's commit in the batch and adds into that level's device row (viol_loop_scan).
+    static constexpr int VN = 16;
+    bool cont = false;
+    std::vector<std::array<uint64_t, VN>> viol_rows;  // [level - 1][invariant bit]
+    uint64_t viol_first[VN];      // global id of each invariant's first violating state (all ones: none)
+    int32_t viol_first_level[VN]; // ... its level (0: none)
+    // ... and, where that state was never appended to a level (a winner of the sharded round that stopped
+    // the run): its parent's global id in viol_first and the slot key that leads to it here
+    uint32_t viol_first_slot[VN];
+    void viol_reset() {
+        viol_rows.clear();
+        for (int b = 0; b < VN; b++) {
+            viol_first[b] = ~0ull;
+            viol_first_level[b] = 0;
+            viol_first_slot[b] = KEY_NONE;
+        }
+    }
+    void viol_alloc() {
+        for (Shard &s : sh) {
+            if (s.viol) continue;
+            s.viol = dmalloc<unsigned long long>(2 * VN);
+            HIPCHK(hipHostMalloc((void **)&s.hviol, 2 * VN * 8, hipHostMallocDefault));
+        }
+    }
+    // the continuation word behind every error-slot set of the shards (KParams::err), before the run's first kernel
+    void viol_flag() {
+        for (Shard &s : sh)
+            for (unsigned long long *e : {s.err, s.alt.err})
+                if (e) HIPCHK(hipMemsetAsync(e + ERR_NSLOTS, cont ? 0x01 : 0, 8, stream));
+    }
+    // device-driven level loop: a row of counts and one of first positions per level of the batch
+    unsigned long long *viol_loop = nullptr;  // [2][LREC_CAP][VN]: counts, then first positions
+    void viol_loop_begin(int K) {
+        if (!viol_loop) viol_loop = dmalloc<unsigned long long>(2ull * LREC_CAP * VN);
+        HIPCHK(hipMemsetAsync(viol_loop, 0, (size_t)K * VN * 8, stream));
+        HIPCHK(hipMemsetAsync(viol_loop + (size_t)LREC_CAP * VN, 0xFF, (size_t)K * VN * 8, stream));
+    }
+    // the scan of the level that the commit of the batch's level i made (enqueued right behind that commit)
+    void viol_loop_scan(Shard &s, const KParams &Qc, int i, uint64_t bound) {
+        KParams Q = Qc;
+        Q.foff = Qc.noff;  // the new level's offsets
+        Q.ctl = nullptr;
+        ks.viol_scan(Q, bound, ViolParams{viol_loop + (size_t)i * VN, viol_loop + ((size_t)LREC_CAP + i) * VN, 0, 1, 1, 0,
+                                          ~0ull, Qc.ctl_next, (uint32_t)i}, stream);
+    }
+    // a level's counts and first level positions (all ones: none) into its row; gbase: its first global id
+    uint32_t viol_add(int level, uint64_t gbase, const unsigned long long *cnt, const unsigned long long *first) {
+        if (viol_rows.size() < (size_t)level) viol_rows.resize((size_t)level, std::array<uint64_t, VN>{});
+        uint32_t fresh = 0;
+        for (int b = 0; b < VN; b++) {
+            viol_rows[(size_t)level - 1][b] += cnt[b];
+            if (cnt[b] && viol_first[b] == ~0ull) {
+                viol_first[b] = gbase + first[b];
+                viol_first_level[b] = level;
+                fresh |= 1u << b;
+            }
+        }
+        return fresh;
+    }
+    void viol_clear() {
+        for (Shard &s : sh) {
+            HIPCHK(hipMemsetAsync(s.viol, 0, VN * 8, stream));
+            HIPCHK(hipMemsetAsync(s.viol + VN, 0xFF, VN * 8, stream));
+        }
+    }
+    // n records at off[] behind word `wbase` of `buf` (a ring of rcap words; all ones: a flat buffer)
+    void viol_scan(Shard &s, const uint32_t *buf, const uint64_t *off, uint64_t wbase, uint64_t rcap, uint64_t n,
+                   uint64_t pos0, uint64_t blk, uint64_t nsh, uint64_t self, uint64_t limit) {
+        if (!n) return;
+        KParams Q = base(s);
+        Q.front = buf;
+        Q.foff = off;
+        Q.fbase = wbase;
+        Q.rcap = rcap;
+        ks.viol_scan(Q, n, ViolParams{s.viol, s.viol + VN, pos0, blk, nsh, self, limit, nullptr, 0u}, stream);
+    }
+    // the scans since viol_clear into the row of `level`, whose first state has global id gbase;
+    // reduce: over the ranks as well (a sharded level; collective).  Returns the invariants whose first
+    // violating state this call found.
+    uint32_t viol_fold(int level, uint64_t gbase, bool reduce) {
+        // nfirst: 2^62 - position, 0 = none (the transports offer a sum and a maximum, of values below 2^63)
+        constexpr uint64_t TOP = 1ull << 62;
+        uint64_t cnt[VN] = {0}, nfirst[VN] = {0};
+        for (Shard &s : sh) HIPCHK(hipMemcpyAsync(s.hviol, s.viol, 2 * VN * 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        for (Shard &s : sh)
+            for (int b = 0; b < VN; b++) {
+                cnt[b] += s.hviol[b];
+                if (s.hviol[VN + b] < TOP) nfirst[b] = std::max<uint64_t>(nfirst[b], TOP - s.hviol[VN + b]);
+            }
+        if (reduce) {
+            allreduce(cnt, VN, false);
+            allreduce(nfirst, VN, true);
+        }
+        unsigned long long c[VN], f[VN];
+        for (int b = 0; b < VN; b++) {
+            c[b] = cnt[b];
+            f[b] = nfirst[b] ? TOP - nfirst[b] : ~0ull;
+        }
+        return viol_add(level, gbase, c, f);
     }
 
     // progress
@@ -1066,7 +1181,8 @@ struct rmc_ctx {
         d_cnt1 = dmalloc<uint32_t>(4);
         d_fp1 = dmalloc<ulonglong2>(ks.maxsucc + 1);
         d_inv = dmalloc<int32_t>(7);
-        d_err1 = dmalloc<unsigned long long>(ERR_NSLOTS);
+        d_err1 = dmalloc<unsigned long long>(ERR_NSLOTS + 1);
+        HIPCHK(hipMemsetAsync(d_err1 + ERR_NSLOTS, 0, 8, stream));
         d_flags1 = dmalloc<uint32_t>(4);
         HIPCHK(hipStreamSynchronize(stream));
     }
@@ -1161,9 +1277,10 @@ struct rmc_ctx {
         s.T_cap = 1ull << (cfg.seen_log2 ? cfg.seen_log2 : 22);
         s.T = dmalloc<ulonglong2>(s.T_cap);
         HIPCHK(hipMemsetAsync(s.T, 0, s.T_cap * 16, stream));
-        s.err = dmalloc<unsigned long long>(ERR_NSLOTS);
+        s.err = dmalloc<unsigned long long>(ERR_NSLOTS + 1);  // (+ the continuation word: viol_flag)
         s.flags = dmalloc<uint32_t>(4);
         HIPCHK(hipMemsetAsync(s.err, 0xFF, ERR_NSLOTS * 8, stream));
+        HIPCHK(hipMemsetAsync(s.err + ERR_NSLOTS, 0, 8, stream));
         HIPCHK(hipMemsetAsync(s.flags, 0, 16, stream));
         s.sum = dmalloc<unsigned long long>(SUM_WORDS_TOTAL);
         HIPCHK(hipMemsetAsync(s.sum, 0, SUM_WORDS_TOTAL * 8, stream));  // (the self-loop stripes are 0 between launches)
@@ -1177,11 +1294,12 @@ struct rmc_ctx {
             a.pnm = dmalloc<uint32_t>(chunk_parents + 1);
             a.hcnt = dmalloc<uint32_t>(chunk_parents + 1);
             a.hoff = dmalloc<uint32_t>(chunk_parents + 1);
-            a.err = dmalloc<unsigned long long>(ERR_NSLOTS);
+            a.err = dmalloc<unsigned long long>(ERR_NSLOTS + 1);
             a.flags = dmalloc<uint32_t>(4);
             a.sum = dmalloc<unsigned long long>(SUM_WORDS_TOTAL);
             HIPCHK(hipMemsetAsync(a.cnt, 0, (chunk_parents + 1) * 4, stream));
             HIPCHK(hipMemsetAsync(a.err, 0xFF, ERR_NSLOTS * 8, stream));
+            HIPCHK(hipMemsetAsync(a.err + ERR_NSLOTS, 0, 8, stream));
             HIPCHK(hipMemsetAsync(a.flags, 0, 16, stream));
             HIPCHK(hipMemsetAsync(a.sum, 0, SUM_WORDS_TOTAL * 8, stream));
             for (hipEvent_t *e : {&s.xdone, &a.done}) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -1206,9 +1324,11 @@ struct rmc_ctx {
         s.ocnt = nullptr;  // (inside sum)
         dfree(s.OT); dfree(s.ob); dfree(s.ib); dfree(s.oside); dfree(s.iside); dfree(s.ooff);
         dfree(s.isz); dfree(s.ioff);
-        dfree(s.err); dfree(s.sum); dfree(s.flags); dfree(s.cov);
+        dfree(s.err); dfree(s.sum); dfree(s.flags); dfree(s.cov); dfree(s.viol);
         if (s.hcov) (void)hipHostFree(s.hcov);
         s.hcov = nullptr;
+        if (s.hviol) (void)hipHostFree(s.hviol);
+        s.hviol = nullptr;
         dfree(s.score); dfree(s.wcnt); dfree(s.wacc); dfree(s.pnm); dfree(s.hcnt); dfree(s.hoff); dfree(s.wposw); dfree(s.ctick);
         dfree(s.bw); dfree(s.bg); dfree(s.boff); dfree(s.bww); dfree(s.boffw); dfree(s.tickets);
         dfree(s.bn); dfree(s.boffn); dfree(s.plist); dfree(s.hctx);
@@ -1244,7 +1364,7 @@ struct rmc_ctx {
         for (Shard &s : sh) free_shard(s, keep_host_trace);
         if (!keep_host_trace) sh.clear();
         dfree(d_info); dfree(d_nat2id); dfree(d_gmsg); dfree(d_seeds);
-        dfree(d_one); dfree(d_init_rec); dfree(d_init_fp); dfree(d_out); dfree(d_keys); dfree(d_cnt1); dfree(d_fp1); dfree(d_inv); dfree(d_err1);
+        dfree(d_one); dfree(d_init_rec); dfree(d_init_fp); dfree(d_out); dfree(d_keys); dfree(d_cnt1); dfree(d_fp1); dfree(d_inv); dfree(d_err1); dfree(viol_loop);
         dfree(d_flags1); dfree(d_red);
         dfree(d_sim_init); dfree(d_sim_len); dfree(d_sim_gen); dfree(d_sim_end); dfree(d_sim_keys); dfree(d_sim_err);
         sim_walks_cap = sim_keys_cap = 0;
@@ -1805,6 +1925,8 @@ struct rmc_ctx {
     int init(rmc_level_stats *st) {
         if (inited) throw Fail(RMC_E_STATE, "rmc_init called twice");
         if (coverage) cov_alloc();
+        if (cont) viol_alloc();
+        viol_flag();
         auto t0 = std::chrono::steady_clock::now();
         std::vector<uint32_t> rec = init_record();
         const uint32_t rw = record_words(rec.data());
@@ -1891,6 +2013,13 @@ struct rmc_ctx {
     int init_verdict(const int32_t *iv, uint32_t rw, std::chrono::steady_clock::time_point t0, rmc_level_stats *st) {
         for (uint32_t o = inv_order; o; o >>= 4) {
             const int b = (int)(o & 15u) - 1;
+            if (iv[b] == 0 && cont) {  // counted (the invariants after it are not evaluated on Init), and on
+                viol_rows.assign(1, std::array<uint64_t, VN>{});
+                viol_rows[0][b] = 1;
+                viol_first[b] = 0;
+                viol_first_level[b] = 1;
+                break;
+            }
             if (iv[b] != 1) {
                 status = iv[b] == 0 ? RMC_VIOLATION : RMC_EVAL_ERROR;
                 violated = b;
@@ -2069,13 +2198,14 @@ struct rmc_ctx {
     // else an internal invariant of the engine that failed (RMC_E_STATE)
     static int flag_code(unsigned long long f) { return (f & 1u) ? RMC_E_CAPACITY : RMC_E_STATE; }
 
-    static int first_error(const unsigned long long *e, unsigned long long *best) {
+    // (continuation on: a FALSE invariant is no error -- its key is not looked at)
+    int first_error(const unsigned long long *e, unsigned long long *best) const {
         int kind = -1;
         *best = ~0ull;
         const int order[4] = {ERR_ASSERT, ERR_DEADLOCK, ERR_INV, ERR_EVAL};
         for (int q = 0; q < 4; q++) {
             const int kk = order[q];
-            if (e[kk] == ~0ull) continue;
+            if (e[kk] == ~0ull || (cont && kk == ERR_INV)) continue;
             if (kind < 0 || (e[kk] >> 8) < (*best >> 8)) { kind = kk; *best = e[kk]; }
         }
         return kind;
@@ -2320,6 +2450,11 @@ struct rmc_ctx {
             queue_at_end = 0;
         }
         if (coverage) HIPCHK(hipMemcpyAsync(s.hcov, s.cov, COV_N * 8, hipMemcpyDeviceToHost, stream));
+        if (cont && s.cur_n) {  // the new level, whole (a replicated level: every rank counts all of it)
+            viol_clear();
+            viol_scan(s, s.R, s.cur_off, s.cur_wbase, s.rcap, s.cur_n, 0, 1, 1, 0, ~0ull);
+            viol_fold(L + 1, gid_nxt, false);
+        }
         HIPCHK(hipStreamSynchronize(stream));  // the trace copies of the level
         if (coverage) cov_add(cov_total, s.hcov);
         st->total_generated = total_generated;
@@ -2408,6 +2543,7 @@ struct rmc_ctx {
         __atomic_store_n(&s.hloop->done, 0u, __ATOMIC_RELAXED);
         __atomic_store_n(&s.hloop->stop, (uint32_t)CTL_RUN, __ATOMIC_RELEASE);
         launch_set_ctl(s.ctl, 2, h, s.sum, stream);
+        if (cont) viol_loop_begin(K);
         uint64_t *offs[2] = {s.cur_off, s.nxt_off};
         std::vector<size_t> mark(K);
         // Levels go in groups of GL.  The loop's progress is mirrored into pinned host memory
@@ -2436,6 +2572,8 @@ struct rmc_ctx {
                 timed(PH_HASH, [&] { ks.fused(Q, stream); });
                 timed(PH_DEDUP, [&] { ks.wincount(Q, DP, stream); });
                 timed(PH_MAT, [&] { ks.commit(Q, stream); });
+                // continuation: the level this commit made, counted before a later level reuses its ring words
+                if (cont) viol_loop_scan(s, Q, i, DP);
             }
         };
         // true once group g has finished (or the loop stopped); a stream error ends the wait
@@ -2503,6 +2641,13 @@ struct rmc_ctx {
         }
         evrecs.clear();
         evused = 0;
+        std::vector<unsigned long long> vrows;
+        if (cont && D) {  // the rows of the levels the loop made
+            vrows.resize(2 * (size_t)D * VN);
+            HIPCHK(hipMemcpy(vrows.data(), viol_loop, (size_t)D * VN * 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(vrows.data() + (size_t)D * VN, viol_loop + (size_t)LREC_CAP * VN, (size_t)D * VN * 8,
+                             hipMemcpyDeviceToHost));
+        }
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < D; i++) {
             const LevelRec &r = s.hlrec[i];
@@ -2516,6 +2661,7 @@ struct rmc_ctx {
             if (r.new_states) {
                 s.level_start.push_back(gid_nxt);
                 depth = L + 1;
+                if (cont) viol_add(L + 1, gid_nxt, &vrows[(size_t)i * VN], &vrows[((size_t)D + i) * VN]);
             } else {
                 finished = true;
                 status = RMC_DONE;
@@ -2660,6 +2806,11 @@ struct rmc_ctx {
             if (winners_before + nxt_before > 0) depth = (int)s.level_start.size() + 1;
         }
         err_last_slot = KEY_NONE;
+        if (cont && total_distinct > gid_nxt) {  // the unfinished level up to TLC's stopping point: the next-level records below `distinct`
+            viol_clear();
+            viol_scan(s, s.R, s.nxt_off, s.nbase(), s.rcap, total_distinct - gid_nxt, 0, 1, 1, 0, ~0ull);
+            viol_fold((int)s.level_start.size() + 1, gid_nxt, false);
+        }
         total_generated += gen;
         st->generated = gen;
         st->new_states = nxt_before + winners_before + ((kind == ERR_INV || kind == ERR_EVAL) ? 1 : 0);
@@ -3285,6 +3436,12 @@ struct rmc_ctx {
         }
         glevel.push_back(gbase + Fg);
         HIPCHK(hipStreamSynchronize(stream));
+        if (cont && level_new) {  // every shard its part of the new level
+            viol_clear();
+            for (Shard &s : sh)
+                viol_scan(s, s.R, s.cur_off, s.cur_wbase, s.rcap, s.cur_n, 0, B, (uint64_t)W, (uint64_t)s.id, ~0ull);
+            viol_fold(L + 1, gbase + Fg, true);
+        }
         if (level_new) {
             depth = L + 1;
         } else {
@@ -3353,6 +3510,48 @@ struct rmc_ctx {
             err_last_slot = KEY_NONE;
             total_distinct += winb;
             if (winb) depth = L + 1;
+        }
+        if (cont && total_distinct > gbase + Fg) {
+            // the unfinished level up to TLC's stopping point: what the earlier rounds appended, and of this
+            // round's winners, still in the outboxes, those of the shards before e and e's own up to the error
+            const uint64_t gnext = gbase + Fg, limit = total_distinct - gnext, B = chunk_parents;
+            std::vector<uint64_t> A(W + 1, level_new);  // this round's winners: shard t's first level position
+            for (int t = 0; t < W; t++) A[t + 1] = A[t] + tab[TAB * t + 1];
+            viol_clear();
+            for (Shard &s : sh) {
+                viol_scan(s, s.R, s.nxt_off, s.nbase(), s.rcap, s.nxt_n, 0, B, (uint64_t)W, (uint64_t)s.id, limit);
+                if (s.id <= e) viol_scan(s, s.ob, s.ooff, 0, ~0ull, A[s.id + 1] - A[s.id], A[s.id], 1, 1, 0, limit);
+            }
+            const uint32_t fresh = viol_fold(L + 1, gnext, true);
+            // a first violating state of the unfinished level cannot be looked up by its global id (the level
+            // has no entry in glevel / level_start yet): its parent and slot key are taken here -- from its
+            // trace entry on the shard it was appended to (local index behind that shard's current level), or,
+            // for one of this round's winners, which have no trace entry, from its sidecar
+            if (fresh) {
+                for (Shard &s : sh) flush_trace(s, s.trace_end);
+                sync_trace();
+                HIPCHK(hipStreamSynchronize(stream));
+            }
+            for (int b = 0; b < VN; b++) {
+                if (!(fresh & (1u << b))) continue;
+                const uint64_t g = viol_first[b] - gnext;
+                uint64_t v[2] = {0, 0};
+                for (Shard &s : sh)
+                    if (g < level_new) {
+                        if ((uint64_t)s.id != (g / B) % (uint64_t)W) continue;
+                        const uint64_t gid = s.level_start[L - 1] + s.cur_n + (g / (B * (uint64_t)W)) * B + g % B;
+                        if (gid >= s.tflushed) throw Fail(RMC_E_STATE, "trace entry not on the host");
+                        v[0] = s.hpar.get(gid);
+                        v[1] = s.hslot.get(gid);
+                    } else if (g >= A[s.id] && g < A[s.id + 1]) {
+                        const uint4 side = d2h(s.oside + (g - A[s.id]));
+                        v[0] = ((uint64_t)side.y << 32) | side.x;
+                        v[1] = side.z & 0xFFFFu;
+                    }
+                allreduce(v, 2, false);
+                viol_first[b] = v[0];
+                viol_first_slot[b] = (uint32_t)v[1];
+            }
         }
         total_generated += gen;
         st->generated = gen;
@@ -3748,6 +3947,8 @@ struct rmc_ctx {
         if (inited) throw Fail(RMC_E_STATE, "resume: needs a context not yet initialised (rmc_create or rmc_reset)");
         if (coverage)
             throw Fail(RMC_E_ARG, "resume: checkpoints do not carry action coverage (rmc_set_coverage is on)");
+        if (cont)
+            throw Fail(RMC_E_ARG, "resume: checkpoints do not carry the violation counts (rmc_set_continue is on)");
         try {
             resume_body(path_arg);
         } catch (...) {
@@ -3958,6 +4159,7 @@ struct rmc_ctx {
         total_generated = total_distinct = queue_at_end = 0;
         std::memset(cov_total, 0, sizeof cov_total);  // (the setting stays)
         std::memset(cov_level, 0, sizeof cov_level);
+        viol_reset();  // (the setting stays)
         violated = -1;
         err_ref = 0;
         err_last_slot = KEY_NONE;
@@ -4039,6 +4241,7 @@ int rmc_create(const rmc_config *cfg, void **out) {
     if (!cfg || !out) return RMC_E_ARG;
     *out = nullptr;
     rmc_ctx *c = new rmc_ctx();
+    c->viol_reset();
     c->cfg = *cfg;
     int rc = guarded(c, [&] {
         c->setup();
@@ -4127,6 +4330,63 @@ int rmc_get_coverage(void *ctx, rmc_coverage *out) {
             out->distinct[k] = c->cov_total[16 + k];
         }
         out->init_generated = out->init_distinct = 1;
+        return RMC_OK;
+    });
+}
+
+int rmc_set_continue(void *ctx, int on) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        if (c->inited) throw Fail(RMC_E_STATE, "rmc_set_continue: after rmc_create or rmc_reset, before rmc_init");
+        c->cont = on != 0;
+        c->viol_flag();  // (also what a later rmc_resume, which does not pass rmc_init, runs with)
+        return RMC_OK;
+    });
+}
+
+int rmc_get_violations(void *ctx, rmc_violations *out) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    if (!out) return RMC_E_ARG;
+    return guarded(c, [&] {
+        if (!c->cont) throw Fail(RMC_E_STATE, "rmc_get_violations: continuation is off (rmc_set_continue)");
+        if (!c->inited) throw Fail(RMC_E_STATE, "rmc_get_violations before rmc_init");
+        std::memset(out, 0, sizeof *out);
+        for (const auto &row : c->viol_rows)
+            for (int b = 0; b < 16; b++) {
+                out->count[b] += row[b];
+                out->total += row[b];
+            }
+        for (int b = 0; b < 16; b++) out->first_level[b] = c->viol_first_level[b];
+        return RMC_OK;
+    });
+}
+
+int rmc_get_violation_levels(void *ctx, uint32_t invariant_bit, uint64_t *per_level, uint32_t cap, uint32_t *n) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    if (!per_level || !n || invariant_bit >= 16) return RMC_E_ARG;
+    return guarded(c, [&] {
+        if (!c->cont) throw Fail(RMC_E_STATE, "rmc_get_violation_levels: continuation is off (rmc_set_continue)");
+        if (!c->inited) throw Fail(RMC_E_STATE, "rmc_get_violation_levels before rmc_init");
+        // one entry per level reached so far (a level nothing violated in: 0)
+        const uint32_t levels = (uint32_t)std::max<size_t>(c->viol_rows.size(), (size_t)std::max(c->depth, 1));
+        if (levels > cap) throw Fail(RMC_E_ARG, "buffer too small");
+        for (uint32_t l = 0; l < levels; l++) per_level[l] = l < c->viol_rows.size() ? c->viol_rows[l][invariant_bit] : 0;
+        *n = levels;
+        return RMC_OK;
+    });
+}
+
+int rmc_violation_trace(void *ctx, uint32_t invariant_bit) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    if (invariant_bit >= 16) return RMC_E_ARG;
+    return guarded(c, [&] {
+        if (!c->cont) throw Fail(RMC_E_STATE, "rmc_violation_trace: continuation is off (rmc_set_continue)");
+        if (!c->inited) throw Fail(RMC_E_STATE, "rmc_violation_trace before rmc_init");
+        if (!c->viol_first_level[invariant_bit]) throw Fail(RMC_E_ARG, "rmc_violation_trace: that invariant has no violation");
+        std::vector<uint16_t> slots = c->path_slots(c->viol_first[invariant_bit], nullptr);
+        if (c->viol_first_slot[invariant_bit] != KEY_NONE) slots.push_back((uint16_t)c->viol_first_slot[invariant_bit]);
+        c->replay_trace(slots);
+        c->trace_from_sim = false;
         return RMC_OK;
     });
 }

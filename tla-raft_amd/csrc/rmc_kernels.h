@@ -145,7 +145,9 @@ struct KParams {
     uint64_t trace_base;
     uint64_t gid_next_base;    // global id of next-level index 0
     uint64_t gid_parent_base;  // global id of level-local parent 0
-    // errors: atomicMin keys (p << 16 | slot), level-local p
+    // errors: atomicMin keys (p << 16 | slot), level-local p; err[ERR_NSLOTS]: non-zero = continuation
+    // (rmc_set_continue), read only by a commit that met a FALSE invariant, which then leaves err[ERR_INV]
+    // alone -- the level's violations are counted by k_viol_scan; an evaluation error is reported as ever
     unsigned long long *err;
     uint32_t *flags;           // [0] msg-cap overflow, [1] violated invariant bit, [2] eval-error invariant bit
     // sharded round (W > 1): expand writes fingerprints only (the owners probe and elect), commit
@@ -253,6 +255,25 @@ struct CoverParams {
     uint32_t bound_grp, bound_kind;  // ErrSlot
 };
 
+// Continuation (rmc_set_continue; TLC's -continue): k_viol_scan counts, per invariant id, the records of a
+// launch that violate it -- cnt[id] += the count, first[id] = min(first[id], level position).  Record i
+// of the launch lies at level position pos0 + ((i / blk) * nsh + self) * blk + i % blk: a shard's part of
+// a block-cyclic level (blk = chunk_parents, nsh = W, self = the shard), or a run of consecutive states
+// (blk = nsh = 1, self = 0).  Records at level positions >= limit are not looked at (the cut at an error
+// that stops the run; all ones: none).
+constexpr int VIOL_INVS = 7;     // the compiled invariants (rmc.h RMC_INV_*)
+// Inside the device-driven level loop (ctl set) the launch follows the commit of the batch's level `iter` and
+// scans the level that commit made, as the control block it wrote describes it (parents, ring position; the
+// records' offsets are P.foff): only if that block stands at iter + 1 levels done -- a level that stopped on
+// an error did not advance it (the host scans that level with its cut), and the no-op launches behind a
+// stopped loop find a block of another count.  cnt / first are then that level's row.
+struct ViolParams {
+    unsigned long long *cnt, *first;
+    uint64_t pos0, blk, nsh, self, limit;
+    const LevelCtl *ctl;
+    uint32_t iter;
+};
+
 struct KernelSet {
     int N, V, MR, MCAP, CCW, RECW_MAX, maxsucc;
     int ctxw;                                                 // hash-context words per parent (split chunks)
@@ -275,6 +296,7 @@ struct KernelSet {
                         uint32_t self, uint64_t g0, unsigned long long *inserted, hipStream_t);
     void (*walk)(const KParams &, const WalkParams &, hipStream_t);  // simulation: one batch of random walks
     void (*cover)(const KParams &, const CoverParams &, hipStream_t);  // coverage: successors generated per action
+    void (*viol_scan)(const KParams &, uint64_t n, const ViolParams &, hipStream_t);  // continuation: violations among n records
     void (*fp_states)(const KParams &, uint64_t n, hipStream_t);  // fp of front[0..n) -> fp
     void (*inv_states)(const KParams &, uint64_t n, int32_t *out, hipStream_t); // per state: 1/0/-1 for inv_mask bits
     // host codec of the packed core (rmc_spec.h Codec)

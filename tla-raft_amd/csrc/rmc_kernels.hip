@@ -3292,7 +3292,7 @@ __global__ __launch_bounds__(64, (N <= 3 && MR == 1) ? RMC_N3_COMMIT_WAVES : 1) 
                 int which = 0;
                 const MsgView mv{P.front, idw, P.rcap, nm, sb.w, sc.x, nadd, P.t.info};
                 const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
-                if (iv != 1) {
+                if (iv != 1 && !(iv == 0 && P.err[ERR_NSLOTS])) {
                     const unsigned long long ek = ((((unsigned long long)p << 16) | key) << 8) | (unsigned long long)which;
                     atomicMin(&P.err[iv == 0 ? ERR_INV : ERR_EVAL], ek);
                 }
@@ -3471,7 +3471,7 @@ __global__ __launch_bounds__(256) void k_commit_split(KParams P) {
             int which = 0;
             const MsgView mv{P.front, pid, P.rcap, nm, sb.w, sc.x, nadd, P.t.info};
             const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
-            if (iv != 1) {
+            if (iv != 1 && !(iv == 0 && P.err[ERR_NSLOTS])) {
                 const unsigned long long ek = ((((unsigned long long)p << 16) | key) << 8) | (unsigned long long)which;
                 atomicMin(&P.err[iv == 0 ? ERR_INV : ERR_EVAL], ek);
             }
@@ -3723,7 +3723,7 @@ __global__ __launch_bounds__(XB_THREADS) void k_commit_items(KParams P) {
                 const uint64_t mids = (P.inv_mask & 32u) ? ring_wrap(ring_wrap(P.fbase + P.foff[p], P.rcap) + CCW, P.rcap) : 0;
                 const MsgView mv{P.front, mids, P.rcap, nm, sb.w, sc.x, nadd, P.t.info};
                 const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
-                if (iv != 1) {
+                if (iv != 1 && !(iv == 0 && P.err[ERR_NSLOTS])) {
                     const unsigned long long ek = ((((unsigned long long)p << 16) | key) << 8) | (unsigned long long)which;
                     atomicMin(&P.err[iv == 0 ? ERR_INV : ERR_EVAL], ek);
                 }
@@ -4011,6 +4011,76 @@ __global__ __launch_bounds__(64) void k_cover(KParams P, CoverParams Cp) {
     if (lane < COV_ACTS && mine) atomicAdd(&Cp.gen[lane], (unsigned long long)mine);
 }
 
+// ---- continuation (rmc_set_continue; TLC's -continue) -----------------------------------------------
+// The violations among n committed records, counted on the side of the BFS: a lane per record
+// (P.front / P.foff / P.fbase / P.rcap name them: a level in the ring, or a sharded round's outbox),
+// grid-strided.  A record's level position follows from its index (ViolParams); those at or past
+// Vp.limit lie beyond TLC's stopping point and are skipped.  The lane decodes the record's core and
+// evaluates the configured invariants in cfg order up to the first that does not hold (check_invs, as
+// the commits do: NoAllCommit reads the record's message ids from where they lie), so a state is
+// attributed to one invariant; an evaluation error is no violation.  Per invariant a wave counts with one
+// ballot, the block gathers its waves in LDS -- the counts, and the smallest level position met -- and
+// adds each invariant it met to Vp.cnt once and takes one minimum on Vp.first: at most two global
+// atomics per block and violated invariant, whatever share of the records violate.
+template <int N, int V, int MR>
+__global__ __launch_bounds__(256) void k_viol_scan(KParams P, uint64_t n, ViolParams Vp) {
+    using S = Spec<N, V, MR>;
+    using Lo = Layout<N, V>;
+    __shared__ uint32_t h[VIOL_INVS];
+    __shared__ unsigned long long f[VIOL_INVS];
+    if (threadIdx.x < VIOL_INVS) {
+        h[threadIdx.x] = 0u;
+        f[threadIdx.x] = ~0ull;
+    }
+    __syncthreads();
+    if (Vp.ctl) {  // device loop: the level the commit before this launch made (block-uniform)
+        if (Vp.ctl->done_levels != Vp.iter + 1u) return;
+        n = Vp.ctl->cur_n;
+        P.fbase = Vp.ctl->cur_wbase;
+    }
+    const int lane = threadIdx.x & 63;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    // (every lane of a wave makes the same number of rounds: the ballots see whole waves)
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += step) {
+        const uint64_t i = base + threadIdx.x;
+        const uint64_t g = Vp.pos0 + ((i / Vp.blk) * Vp.nsh + Vp.self) * Vp.blk + i % Vp.blk;
+        int which = -1;
+        if (i < n && g < Vp.limit) {
+            const uint64_t start = rec_start<S::RECW_MAX>(P, i);
+            uint32_t packed[S::CCW], c[Lo::NW];
+#pragma unroll
+            for (int k = 0; k < S::CCW; k++) packed[k] = ring_word(P.front, start, (uint32_t)k, P.rcap);
+            decode_core<N, V>(packed, c);
+            const MsgView mv{P.front, ring_wrap(start + S::CCW, P.rcap), P.rcap, (c[Lo::W_MISC] >> 16) & 0xFFu,
+                             0u, 0u, 0u, P.t.info};
+            int w = 0;
+            if (check_invs<N, V>(c, P.inv_order, &w, mv) == 0) which = w;
+        }
+        if (!__ballot(which >= 0)) continue;
+#pragma unroll
+        for (int b = 0; b < VIOL_INVS; b++) {
+            const uint64_t m = __ballot(which == b);
+            if (!m) continue;
+            // (level positions grow with the lane inside a block of Vp.blk records but not across one: the
+            // wave's smallest, not its first lane's)
+            unsigned long long mine = which == b ? (unsigned long long)g : ~0ull;
+            for (int d = 32; d >= 1; d >>= 1) {
+                const unsigned long long o = __shfl_xor(mine, d, 64);
+                mine = o < mine ? o : mine;
+            }
+            if (lane == 0) {
+                atomicAdd(&h[b], (uint32_t)__popcll(m));
+                atomicMin(&f[b], mine);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < VIOL_INVS && h[threadIdx.x]) {
+        atomicAdd(&Vp.cnt[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+        atomicMin(&Vp.first[threadIdx.x], f[threadIdx.x]);
+    }
+}
+
 static inline unsigned grid_for(uint64_t n) {
     const uint64_t cap = 256ull * RMC_GRID_PER_CU;  // one-wave blocks per CU (default 32) on 256 CUs
     return (unsigned)(n < cap ? (n ? n : 1) : cap);
@@ -4104,6 +4174,10 @@ struct Launch {
     static void cover(const KParams &P, const CoverParams &cp, hipStream_t s) {
         hipLaunchKernelGGL((k_cover<N, V, MR, BFV>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64), bm_bytes(P), s, P, cp);
     }
+    static void viol(const KParams &P, uint64_t n, const ViolParams &vp, hipStream_t s) {
+        const uint64_t b = (n + 255) / 256;
+        if (n) hipLaunchKernelGGL((k_viol_scan<N, V, MR>), dim3((unsigned)(b < 4096 ? b : 4096)), dim3(256), 0, s, P, n, vp);
+    }
     static void fps(const KParams &P, uint64_t n, hipStream_t s) {
         hipLaunchKernelGGL((k_fp_states<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n);
     }
@@ -4132,6 +4206,7 @@ static void fill(KernelSet *ks) {
     ks->local_flags = &Launch<N, V, MR, BFV>::local_flags;
     ks->walk = &Launch<N, V, MR, BFV>::walk;
     ks->cover = &Launch<N, V, MR, BFV>::cover;
+    ks->viol_scan = &Launch<N, V, MR>::viol;
     ks->fp_states = &Launch<N, V, MR>::fps;
     ks->inv_states = &Launch<N, V, MR>::invs;
     ks->encode = &Launch<N, V, MR>::enc;

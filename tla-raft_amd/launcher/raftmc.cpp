@@ -2,6 +2,7 @@
 //
 //   raftmc [-deadlock] [-workers N] [-config Raft.cfg] [-device D] [-gpus N] [-msgcap C] [-seenlog2 K] Raft.tla
 //   raftmc -coverage MIN ... Raft.tla   (TLC's -coverage: the per-action distinct:generated report at the end)
+//   raftmc -continue ... Raft.tla       (TLC's -continue: search past invariant violations, count them per invariant)
 //   raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config Raft.cfg] [-device D] [-msgcap C] Raft.tla
 //
 // Accepts the flags myrun.sh passes to TLC (myrun.sh:3), reads the same Raft.tla /
@@ -222,11 +223,13 @@ struct Printer {
 int usage(const char *msg) {
     std::fprintf(stderr, "raftmc: %s\nusage: raftmc [-deadlock] [-workers N] [-config FILE.cfg] [-device D] "
                          "[-gpus N [-onerank] [-shardmin K]] [-msgcap C] [-seenlog2 K] [-checkpoint MIN] [-metadir DIR] "
-                         "[-recover DIR] [-coverage MIN] FILE.tla\n"
+                         "[-recover DIR] [-coverage MIN] [-continue] FILE.tla\n"
                          "       raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config FILE.cfg] [-device D] "
                          "[-msgcap C] FILE.tla\n"
                          "  -coverage MIN  per-action coverage (distinct:generated) at the end of the search; the interval "
                          "is parsed as TLC's, only the final report is printed\n"
+                         "  -continue  search past invariant violations: per violated invariant the first behaviour and the "
+                         "number of violating states (TLC prints every one); exit code 12 if any\n"
                          "  -simulate  random behaviours instead of the breadth-first search; num=N of them (default "
                          "1000000; TLC's default is unbounded)\n"
                          "  -depth D   states per behaviour at most (default 100, as TLC)\n"
@@ -425,6 +428,7 @@ int main(int argc, char **argv) {
     unsigned long long sim_num = 1000000, sim_seed = 0;  // (TLC's -simulate is unbounded without num=)
     long long sim_depth = 100;                           // TLC -depth
     bool coverage = false, cov_bad = false;              // TLC -coverage <minutes>
+    bool cont = false;                                   // TLC -continue
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *f) -> const char * {
@@ -455,7 +459,8 @@ int main(int argc, char **argv) {
             char *end = nullptr;
             if (i + 1 >= argc || !isdigit((unsigned char)argv[i + 1][0])) cov_bad = true;
             else if (std::strtod(argv[++i], &end), *end) cov_bad = true;
-        } else if (a == "-depth") sim_depth = std::atoll(need("-depth"));
+        } else if (a == "-continue") cont = true;
+        else if (a == "-depth") sim_depth = std::atoll(need("-depth"));
         else if (a == "-seed") { sim_seed = (unsigned long long)std::strtoll(need("-seed"), nullptr, 10); seed_given = true; }
         else if (a == "-metadir") metadir = need("-metadir");
         else if (a == "-recover") recover_dir = need("-recover");
@@ -469,6 +474,10 @@ int main(int argc, char **argv) {
         if (cov_bad) return usage("-coverage takes a number of minutes");
         if (simulate) return usage("-coverage cannot be combined with -simulate");
         if (!recover_dir.empty()) return usage("-coverage cannot be combined with -recover (checkpoints do not carry it)");
+    }
+    if (cont) {  // refused before anything touches a device
+        if (simulate) return usage("-continue cannot be combined with -simulate");
+        if (!recover_dir.empty()) return usage("-continue cannot be combined with -recover (checkpoints do not carry the violation counts)");
     }
     if (simulate) {  // refused before anything touches a device
         if (sim_bad) return usage("-simulate takes num=N with N >= 1");
@@ -531,15 +540,28 @@ int main(int argc, char **argv) {
     std::printf("Starting... (%s)\n", now_str().c_str());
     // TLC's error lines and "The behavior up to this point is:" block for the context's trace; returns
     // TLC's exit code for the status
-    auto print_error = [&](void *ctx, const rmc_config &cfg, int status, int violated, uint32_t trace_len) -> int {
+    // the name the cfg used for an invariant (Inv and LeaderHasAllCommittedEntries share bit 0)
+    auto inv_name = [&](int bit) -> std::string {
+        std::string name = kInvNames[bit];
+        for (const std::string &n : pm.invariant_names)
+            if ((bit == 0 && (n == "Inv" || n == "LeaderHasAllCommittedEntries")) || n == kInvNames[bit]) name = n;
+        return name;
+    };
+    // a behaviour read out of the context (rmc_trace_state), kept while the context's current trace changes
+    struct Step { std::vector<int32_t> buf; int32_t a, s, w; };
+    auto read_trace = [&](void *ctx, uint32_t trace_len) {
+        std::vector<Step> out;
+        for (uint32_t i = 0; i < trace_len; i++) {
+            Step st{std::vector<int32_t>(RMC_UNPACKED_INTS(5, 3, 256)), 0, 0, 0};
+            if (rmc_trace_state(ctx, i, st.buf.data(), st.buf.size(), &st.a, &st.s, &st.w) < 0) break;
+            out.push_back(std::move(st));
+        }
+        return out;
+    };
+    auto print_error = [&](const std::vector<Step> &steps, const rmc_config &cfg, int status, int violated) -> int {
         int exit_code = 0;
         if (status == RMC_VIOLATION) {
-            // the name the cfg used for the violated invariant (Inv and LeaderHasAllCommittedEntries share bit 0)
-            std::string name = kInvNames[violated];
-            for (const std::string &n : pm.invariant_names)
-                if ((violated == 0 && (n == "Inv" || n == "LeaderHasAllCommittedEntries")) || n == kInvNames[violated])
-                    name = n;
-            std::printf("Error: Invariant %s is violated.\n", name.c_str());
+            std::printf("Error: Invariant %s is violated.\n", inv_name(violated).c_str());
             exit_code = 12;
         } else if (status == RMC_ASSERT) {
             std::printf("Error: The first argument of Assert evaluated to FALSE; the second argument was:\n\"split brain\"\n");
@@ -557,12 +579,10 @@ int main(int argc, char **argv) {
         names.insert(names.end(), kBfNames, kBfNames + 3);  // 13..15
         std::vector<Loc> locs = action_locations(tla, names);
         Printer pr{pm, cfg.n_servers, cfg.n_vals};
-        std::vector<int32_t> buf(RMC_UNPACKED_INTS(5, 3, 256));
         std::vector<int32_t> prev_role(cfg.n_servers, 0);
-        for (uint32_t i = 0; i < trace_len; i++) {
-            int32_t a, s, w;
-            int nints = rmc_trace_state(ctx, i, buf.data(), buf.size(), &a, &s, &w);
-            if (nints < 0) break;
+        for (uint32_t i = 0; i < (uint32_t)steps.size(); i++) {
+            const std::vector<int32_t> &buf = steps[i].buf;
+            const int32_t a = steps[i].a, s = steps[i].s;
             if (a < 0) std::printf("State %u: <Initial predicate>\n", i + 1);
             else {
                 const int an = (a == 12 && s >= 0 && s < cfg.n_servers) ? 13 + prev_role[s] : a;  // role: 0 F, 1 C, 2 L
@@ -598,6 +618,11 @@ int main(int argc, char **argv) {
     if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d)\n", rc); return 75; }
     rmc_level_stats st;
     if (coverage && rmc_set_coverage(ctx, 1) < 0) {
+        std::printf("Error: %s\n", rmc_last_error(ctx));
+        rmc_destroy(ctx);
+        return 75;
+    }
+    if (cont && rmc_set_continue(ctx, 1) < 0) {
         std::printf("Error: %s\n", rmc_last_error(ctx));
         rmc_destroy(ctx);
         return 75;
@@ -675,8 +700,36 @@ int main(int argc, char **argv) {
     rmc_result res;
     rmc_get_result(ctx, &res);
     int exit_code = 0;
-    if (res.status == RMC_DONE) std::printf("Model checking completed. No error has been found.\n");
-    else exit_code = print_error(ctx, cfg, res.status, res.violated, res.trace_len);
+    bool violations = false;
+    // the stopping error's behaviour, read before the violation blocks replace the context's current trace
+    const std::vector<Step> err_steps = res.status == RMC_DONE ? std::vector<Step>() : read_trace(ctx, res.trace_len);
+    if (cont) {
+        // -continue: per violated invariant, in cfg order, TLC's error block for the first violating
+        // behaviour and the number of states that violate it (TLC prints a behaviour per state; a search
+        // that can meet a hundred million of them prints one and counts the rest)
+        rmc_violations vs;
+        if (rmc_get_violations(ctx, &vs) < 0) std::printf("Error: no violation counts: %s\n", rmc_last_error(ctx));
+        else
+            for (uint32_t o = cfg.invariant_order; o; o >>= 4) {
+                const int b = (int)(o & 15u) - 1;
+                if (!vs.count[b]) continue;
+                violations = true;
+                uint32_t tl = 0;
+                if (rmc_violation_trace(ctx, (uint32_t)b) < 0 || rmc_trace_len(ctx, &tl) < 0) {
+                    std::printf("Error: %s\n", rmc_last_error(ctx));
+                    continue;
+                }
+                print_error(read_trace(ctx, tl), cfg, RMC_VIOLATION, b);
+                std::printf("Invariant %s is violated by %llu distinct states (first at depth %d; the first behaviour is "
+                            "shown).\n", inv_name(b).c_str(), (unsigned long long)vs.count[b], vs.first_level[b]);
+            }
+        if (violations) exit_code = 12;
+    }
+    if (res.status == RMC_DONE) {
+        if (!violations) std::printf("Model checking completed. No error has been found.\n");
+    } else {
+        exit_code = print_error(err_steps, cfg, res.status, res.violated);
+    }
     rmc_coverage cov;
     const int cov_rc = coverage && cfg.rank == 0 ? rmc_get_coverage(ctx, &cov) : RMC_OK;
     if (cov_rc < 0) std::printf("Error: no coverage statistics: %s\n", rmc_last_error(ctx));
@@ -756,7 +809,7 @@ int main(int argc, char **argv) {
         } else {
             uint32_t tl = 0;
             rmc_trace_len(ctx, &tl);
-            exit_code = print_error(ctx, cfg, sr.status, sr.violated, tl);
+            exit_code = print_error(read_trace(ctx, tl), cfg, sr.status, sr.violated);
             std::printf("The error is in behaviour %llu (%u states) of seed %llu.\n", (unsigned long long)sr.err_walk,
                         sr.err_len, sim_seed);
         }

@@ -98,6 +98,10 @@ class _Coverage(ctypes.Structure):
                 ("init_generated", ctypes.c_uint64), ("init_distinct", ctypes.c_uint64)]
 
 
+class _Violations(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint64 * 16), ("first_level", ctypes.c_int32 * 16), ("total", ctypes.c_uint64)]
+
+
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 _ALLREDUCE = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, _U64P, ctypes.c_int32, ctypes.c_int32)
 _ALLGATHER = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, _U64P, ctypes.c_int32, _U64P)
@@ -161,6 +165,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "rmc_set_coverage"):
         lib.rmc_set_coverage.argtypes = [vp, i32]
         lib.rmc_get_coverage.argtypes = [vp, P(_Coverage)]
+    if hasattr(lib, "rmc_set_continue"):  # (likewise)
+        lib.rmc_set_continue.argtypes = [vp, i32]
+        lib.rmc_get_violations.argtypes = [vp, P(_Violations)]
+        lib.rmc_get_violation_levels.argtypes = [vp, u32, P(u64), u32, P(u32)]
+        lib.rmc_violation_trace.argtypes = [vp, u32]
     _lib = lib
     return lib
 
@@ -683,6 +692,42 @@ class ModelChecker:
         for a, name in enumerate(ACTIONS):
             out[name] = (c.distinct[a], c.generated[a])
         return out
+
+    def set_continue(self, on: bool = True) -> None:
+        """TLC's -continue: search past invariant violations and count them per invariant (include/rmc.h
+        rmc_set_continue).  On a fresh or reset checker, before init() / run()."""
+        if not hasattr(self.lib, "rmc_set_continue"):
+            raise RmcError("this librmc.so has no continuation (rmc_set_continue): rebuild it")
+        self._check(self.lib.rmc_set_continue(self.h, 1 if on else 0))
+
+    @staticmethod
+    def _inv_bit(name: str) -> int:
+        return INVARIANT_BY_BIT.index("Inv" if name == "LeaderHasAllCommittedEntries" else name)
+
+    def violations(self) -> dict:
+        """{invariant name: (count, first_level or None)} over the configured invariants in cfg order: the
+        explored states attributed to each (the first FALSE one in cfg order) over the levels finished so
+        far, and the level of the first of them in TLC -workers 1 order."""
+        v = _Violations()
+        self._check(self.lib.rmc_get_violations(self.h, ctypes.byref(v)))
+        out = {}
+        for name in self.cfg.invariants:
+            b = self._inv_bit(name)
+            out[name] = (v.count[b], v.first_level[b] or None)
+        return out
+
+    def violation_levels(self, name: str) -> List[int]:
+        """The invariant's violation count per BFS level ([0]: Init's level); sums to its count."""
+        cap = 4096
+        buf, n = (ctypes.c_uint64 * cap)(), ctypes.c_uint32()
+        self._check(self.lib.rmc_get_violation_levels(self.h, self._inv_bit(name), buf, cap, ctypes.byref(n)))
+        return list(buf[:n.value])
+
+    def violation_trace(self, name: str) -> List[Tuple[Optional[Tuple[int, int, int]], dict]]:
+        """The behaviour from Init to the invariant's first violating state, as trace() returns one (it
+        becomes the current trace)."""
+        self._check(self.lib.rmc_violation_trace(self.h, self._inv_bit(name)))
+        return self.trace()
 
     def trace(self) -> List[Tuple[Optional[Tuple[int, int, int]], dict]]:
         n = ctypes.c_uint32()
