@@ -381,6 +381,46 @@ int rmc_get_violations(void *ctx, rmc_violations *out);
 int rmc_get_violation_levels(void *ctx, uint32_t invariant_bit, uint64_t *per_level, uint32_t cap, uint32_t *n);
 int rmc_violation_trace(void *ctx, uint32_t invariant_bit);
 
+/* ---- state graph (TLC's -dump FILE / -dump dot FILE) ------------------------------------------------
+ * The states a run finds and every resolved edge between them, streamed to callbacks while the search runs.
+ * The search itself knows only the BFS tree (each state's parent and slot key); with graph mode on, every
+ * finished level is visited again on the side: its new states go into a map from fingerprint to global id
+ * (a device table of its own; the seen set, the election and the commits are untouched), then its parents
+ * are re-evaluated in chunks and each successor -- duplicates and self-loops included, Next's order -- is
+ * looked up there.
+ *   states(user, gid0, n, unpacked, stride_ints)  the states with global ids gid0 .. gid0 + n - 1 (BFS order,
+ *       Init = 0) in the unpacked layout below, stride_ints apart: the record the search stored, i.e. the
+ *       first-found member of its SYMMETRY/VIEW class, which is what TLC dumps.  NULL: states are not copied.
+ *   edges(user, n, src, key, dst)  n edges in TLC -workers 1 order (ascending src, each src's successors in
+ *       Next's order): global ids and the key in rmc_successors' format.  A successor in its parent's class has
+ *       dst == src.  NULL: the pass runs and nothing is delivered.
+ * Order of delivery: rmc_init delivers states(0, 1, Init); each step that expands level L first delivers the
+ * states of the level it made, ascending, then level L's edges.  A callback that returns non-zero fails
+ * the step with RMC_E_SINK and ends the run (rmc_destroy / rmc_reset may follow).
+ * Without an error the number of edges is `generated` - 1.  At an error the edges stop where TLC -workers 1
+ * stops: the parents before the erring parent p give all their edges; p gives, for an invariant violation or
+ * an evaluation error, the edges up to and including the erring successor, for UpdateTerm's Assert those of
+ * the sub-action batches before the failing one, for a deadlock none; later parents give nothing; the
+ * states delivered are those with global id below the reported `distinct`, so every dst < distinct.
+ * Limits: single GPU (RMC_E_ARG with world_size > 1 or virtual_shards > 1).  The pass reads level L after
+ * level L + 1 is complete, so both stay resident in the frontier ring: a run whose seen set would move to
+ * its compact form (2^compact_log2 slots; the default 2^27 is about 67 M states) fails that step with
+ * RMC_E_MEMORY -- raise compact_log2.  Levels run one per host round trip (device_levels has no effect on the
+ * results).  It composes with coverage and with continuation (the graph is then that of the search that did
+ * not stop).  Checkpoints do not carry the map: rmc_resume with graph mode on returns RMC_E_ARG.
+ * rmc_set_graph: after rmc_create or rmc_reset and before rmc_init (RMC_E_STATE otherwise); NULL = off (nothing more is
+ * launched; what graph mode had allocated stays with the context for a later rmc_set_graph, until rmc_destroy).
+ * rmc_reset keeps the setting and empties the map.  Off by default, and then nothing is allocated or launched. */
+#define RMC_E_SINK -8   /* a graph sink callback returned non-zero */
+typedef struct rmc_graph_sink {
+    void *user;
+    int32_t (*states)(void *user, uint64_t gid0, uint64_t n, const int32_t *unpacked, size_t stride_ints);
+    int32_t (*edges)(void *user, uint64_t n, const uint64_t *src, const uint32_t *key, const uint64_t *dst);
+    uint32_t chunk_parents;  /* parents per edge launch, 0 = auto (8192) */
+    uint32_t map_log2;       /* initial gid-map slots = 2^map_log2, 0 = auto (16); kept at load <= 1/2 by rehashing */
+} rmc_graph_sink;
+int rmc_set_graph(void *ctx, const rmc_graph_sink *sink);
+
 /* Measurement support (bench.py): the random-probe peak of the seen-set layout -- `probes`
  * one-slot reads of 16-B slots at uniformly random indices of a 2^table_log2-slot table,
  * best of 3 timed launches; no model-checking state is touched. */

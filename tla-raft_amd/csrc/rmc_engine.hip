@@ -706,6 +706,179 @@ struct rmc_ctx {
         return viol_add(level, gbase, c, f);
     }
 
+    // ---- graph mode (rmc_set_graph; TLC's -dump) ---------------------------------------------------
+    // Off by default: nothing below is allocated or launched.  On, every finished level is visited twice
+    // more on the side of the search, while both it and the level it made stand in the ring (graph_level):
+    // the new level's records are fingerprinted into the gid map (k_gid_insert) and, with a states
+    // callback, copied back and unpacked; then the expanded level's parents are re-evaluated in chunks
+    // (k_edges: count pass, exclusive scan, write pass), each chunk's edges copied to pinned memory and
+    // handed to the sink.  Single GPU, one level per host round trip (batch_ok), no compact seen set: the
+    // ring at its budget reuses the expanded chunks' words, so migrate_compact fails the step instead.
+    bool graph = false;
+    rmc_graph_sink gsink{};
+    GSlot *gmap = nullptr;
+    uint64_t gmap_cap = 0, gmap_count = 0;
+    uint32_t *g_cnt = nullptr, *g_off = nullptr, *g_key = nullptr, *g_flag = nullptr, *hg_key = nullptr, *hg_word = nullptr;
+    unsigned long long *g_src = nullptr, *g_dst = nullptr, *hg_src = nullptr, *hg_dst = nullptr;
+    uint64_t g_par_cap = 0, g_edge_cap = 0;
+    void *g_tmp = nullptr;
+    size_t g_tmp_bytes = 0;
+    uint64_t graph_chunk() const { return gsink.chunk_parents ? std::min<uint64_t>(gsink.chunk_parents, 1u << 20) : 8192; }
+    GidMap gid_map() const { return GidMap{gmap, gmap_cap - 1}; }
+    void graph_free() {
+        dfree(gmap); dfree(g_cnt); dfree(g_off); dfree(g_key); dfree(g_flag); dfree(g_src); dfree(g_dst); dfree(g_tmp);
+        for (void *p : {(void *)hg_key, (void *)hg_word, (void *)hg_src, (void *)hg_dst})
+            if (p) (void)hipHostFree(p);
+        hg_key = hg_word = nullptr;
+        hg_src = hg_dst = nullptr;
+        gmap_cap = gmap_count = g_par_cap = g_edge_cap = 0;
+        g_tmp_bytes = 0;
+    }
+    void graph_alloc() {
+        if (!gmap) {
+            gmap_cap = 1ull << (gsink.map_log2 ? gsink.map_log2 : 16);
+            gmap = dmalloc<GSlot>(gmap_cap);
+            HIPCHK(hipMemsetAsync(gmap, 0, gmap_cap * sizeof(GSlot), stream));
+            gmap_count = 0;
+        }
+        if (!g_flag) {
+            g_flag = dmalloc<uint32_t>(1);
+            HIPCHK(hipHostMalloc((void **)&hg_word, 16, hipHostMallocDefault));
+        }
+        const uint64_t cp = graph_chunk() + 1;
+        if (cp > g_par_cap) {
+            dfree(g_cnt);
+            dfree(g_off);
+            g_cnt = dmalloc<uint32_t>(cp);
+            g_off = dmalloc<uint32_t>(cp);
+            g_par_cap = cp;
+            size_t t = 0;
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, g_cnt, g_off, (int)cp, stream));
+            if (t > g_tmp_bytes) {
+                dfree(g_tmp);
+                g_tmp = dmalloc<uint8_t>(t);
+                g_tmp_bytes = t;
+            }
+        }
+    }
+    // room for `need` states at load <= 1/2: a larger table, the entries rehashed into it
+    void graph_map_reserve(uint64_t need) {
+        if (need * 2 <= gmap_cap) return;
+        uint64_t nc = gmap_cap;
+        while (need * 2 > nc) nc *= 2;
+        GSlot *nt = dmalloc<GSlot>(nc);
+        HIPCHK(hipMemsetAsync(nt, 0, nc * sizeof(GSlot), stream));
+        launch_gid_rehash(gmap, gmap_cap, GidMap{nt, nc - 1}, stream);
+        HIPCHK(hipStreamSynchronize(stream));
+        dfree(gmap);
+        gmap = nt;
+        gmap_cap = nc;
+    }
+    void graph_edge_reserve(uint64_t need) {
+        if (need <= g_edge_cap) return;
+        HIPCHK(hipStreamSynchronize(stream));
+        const uint64_t nc = std::max<uint64_t>(need + need / 2, 1024);
+        dfree(g_src); dfree(g_dst); dfree(g_key);
+        for (void *p : {(void *)hg_key, (void *)hg_src, (void *)hg_dst})
+            if (p) (void)hipHostFree(p);
+        hg_key = nullptr;
+        hg_src = hg_dst = nullptr;
+        g_edge_cap = 0;
+        g_src = dmalloc<unsigned long long>(nc);
+        g_dst = dmalloc<unsigned long long>(nc);
+        g_key = dmalloc<uint32_t>(nc);
+        HIPCHK(hipHostMalloc((void **)&hg_src, nc * 8, hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void **)&hg_dst, nc * 8, hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void **)&hg_key, nc * 4, hipHostMallocDefault));
+        g_edge_cap = nc;
+    }
+    // n records at off[] behind ring word `wbase`, global ids gid0 ..: into the map, then to the states callback
+    void graph_states(Shard &s, const uint64_t *off, uint64_t wbase, uint64_t n, uint64_t gid0) {
+        if (!n) return;
+        graph_map_reserve(gmap_count + n);
+        KParams Q = base(s);
+        Q.front = s.R;
+        Q.foff = off;
+        Q.fbase = wbase;
+        Q.rcap = s.rcap;
+        ks.gid_insert(Q, n, gid_map(), gid0, stream);
+        gmap_count += n;
+        if (!gsink.states) return;
+        const size_t stride = RMC_UNPACKED_INTS(N, V, ks.MCAP);
+        constexpr uint64_t PIECE = 4096;
+        std::vector<uint64_t> ho;
+        std::vector<uint32_t> hw;
+        std::vector<int32_t> out;
+        for (uint64_t a = 0; a < n; a += PIECE) {
+            const uint64_t k = std::min(PIECE, n - a);
+            ho.resize(k);
+            HIPCHK(hipMemcpyAsync(ho.data(), off + a, k * 8, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            const uint64_t lo = ho[0], words = std::min<uint64_t>(ho[k - 1] + (uint64_t)RECW - lo, s.rcap);
+            hw.assign(words + (uint64_t)RECW, 0u);
+            const uint64_t from = ring_wrap(ring_wrap(wbase, s.rcap) + lo, s.rcap), n1 = std::min(words, s.rcap - from);
+            HIPCHK(hipMemcpyAsync(hw.data(), s.R + from, n1 * 4, hipMemcpyDeviceToHost, stream));
+            if (words > n1) HIPCHK(hipMemcpyAsync(hw.data() + n1, s.R, (words - n1) * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            out.assign(k * stride, 0);
+            for (uint64_t i = 0; i < k; i++) {
+                const std::vector<int32_t> u = unpack(hw.data() + (ho[i] - lo));
+                std::memcpy(out.data() + i * stride, u.data(), std::min(u.size(), stride) * sizeof(int32_t));
+            }
+            if (gsink.states(gsink.user, gid0 + a, k, out.data(), stride))
+                throw Fail(RMC_E_SINK, "the graph sink's states callback failed");
+        }
+    }
+    // the edges of the current level's parents [0, n_par), cut at (bound_pos, bound_key, kind) -- bound_pos all
+    // ones: no cut --, chunk by chunk to the edges callback
+    void graph_edges(Shard &s, uint64_t gid_cur, uint64_t n_par, uint64_t bound_pos, uint32_t bound_key, int kind) {
+        const uint64_t cp = graph_chunk();
+        for (uint64_t p0 = 0; p0 < n_par; p0 += cp) {
+            const uint64_t p1 = std::min(n_par, p0 + cp), np_ = p1 - p0;
+            KParams Q = base(s);
+            ring_params(s, Q);
+            Q.p_begin = p0;
+            Q.p_end = p1;
+            Q.gid_parent_base = gid_cur;
+            EdgeParams E{gid_map(), g_cnt, nullptr, g_src, g_dst, g_key, g_flag, p0, bound_pos, bound_key, (uint32_t)kind};
+            ks.edges(Q, E, stream);
+            HIPCHK(hipMemsetAsync(g_cnt + np_, 0, 4, stream));
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(g_tmp, g_tmp_bytes, g_cnt, g_off, (int)(np_ + 1), stream));
+            HIPCHK(hipMemcpyAsync(hg_word, g_off + np_, 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            const uint64_t total = hg_word[0];
+            if (!total) continue;
+            graph_edge_reserve(total);
+            E.src = g_src; E.dst = g_dst; E.key = g_key;
+            E.off = g_off;
+            HIPCHK(hipMemsetAsync(g_flag, 0, 4, stream));
+            ks.edges(Q, E, stream);
+            HIPCHK(hipMemcpyAsync(hg_src, g_src, total * 8, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(hg_key, g_key, total * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(hg_dst, g_dst, total * 8, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(hg_word + 1, g_flag, 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            HIPCHK(hipGetLastError());
+            if (hg_word[1] & 1u) throw Fail(RMC_E_STATE, "graph: edge to an unknown state (a successor's fingerprint is not in the gid map)");
+            if (hg_word[1]) throw Fail(RMC_E_STATE, "graph: internal: a parent's successors do not fit the edge pass");
+            if (gsink.edges && gsink.edges(gsink.user, total, (const uint64_t *)hg_src, hg_key, (const uint64_t *)hg_dst))
+                throw Fail(RMC_E_SINK, "the graph sink's edges callback failed");
+        }
+    }
+    // Level L (the shard's current level, n_par parents of it) was expanded and the first n_new states of the
+    // level it made stand behind it in the ring: those states first, then level L's edges.  A failure ends the run.
+    void graph_level(Shard &s, uint64_t gid_cur, uint64_t n_par, uint64_t gid_nxt, uint64_t n_new, uint64_t bound_pos,
+                     uint32_t bound_key, int kind) {
+        try {
+            graph_states(s, s.nxt_off, s.nbase(), n_new, gid_nxt);
+            graph_edges(s, gid_cur, n_par, bound_pos, bound_key, kind);
+        } catch (const Fail &e) {
+            finished = true;
+            status = e.code;
+            throw;
+        }
+    }
+
     // progress
     bool inited = false, finished = false;
     bool device_released = false;  // rmc_release_device: only rmc_destroy may follow
@@ -1366,6 +1539,7 @@ struct rmc_ctx {
         dfree(d_info); dfree(d_nat2id); dfree(d_gmsg); dfree(d_seeds);
         dfree(d_one); dfree(d_init_rec); dfree(d_init_fp); dfree(d_out); dfree(d_keys); dfree(d_cnt1); dfree(d_fp1); dfree(d_inv); dfree(d_err1); dfree(viol_loop);
         dfree(d_flags1); dfree(d_red);
+        graph_free();
         dfree(d_sim_init); dfree(d_sim_len); dfree(d_sim_gen); dfree(d_sim_end); dfree(d_sim_keys); dfree(d_sim_err);
         sim_walks_cap = sim_keys_cap = 0;
         if (h_red) (void)hipHostFree(h_red);
@@ -1523,6 +1697,11 @@ struct rmc_ctx {
     }
 
     void migrate_compact(Shard &s, uint64_t need) {
+        if (graph)
+            throw Fail(RMC_E_MEMORY, "graph mode keeps both levels resident in the frontier ring, which the compact seen set's "
+                                     "fixed ring does not: the limit is 2^" + std::to_string(full_max_log2()) +
+                                     " seen-set slots (about " + std::to_string((1ull << full_max_log2()) / 2) +
+                                     " states); rmc_config.compact_log2 can be raised");
         const uint64_t local = sh.size();
         ensure_chunk(s, Gcap);  // the budget below is what the full chunk buffers leave
         HIPCHK(hipStreamSynchronize(stream));
@@ -1948,6 +2127,17 @@ struct rmc_ctx {
             s.T_count = 1;
         } else {
             init_full(rec, rw, iv);
+        }
+        if (graph) {  // Init into the gid map and to the sink
+            graph_alloc();
+            try {
+                graph_states(sh[0], sh[0].cur_off, sh[0].cur_wbase, 1, 0);
+            } catch (const Fail &e) {  // as graph_level: a failure ends the run (Init's level is in place: no second rmc_init)
+                inited = true;
+                finished = true;
+                status = e.code;
+                throw;
+            }
         }
         total_generated = 1;  // TLC counts the initial state as generated
         total_distinct = 1;
@@ -2441,6 +2631,8 @@ struct rmc_ctx {
                          (unsigned long long)level_hfp, (unsigned long long)level_drop);
         st->new_states = s.nxt_n;
         st->new_bytes = s.nxt_words * 4;
+        // graph mode: the new level's states, then this level's edges, while both stand in the ring
+        if (graph) graph_level(s, gid_cur, s.cur_n, gid_nxt, s.nxt_n, ~0ull, 0u, 0);
         end_level(s, gid_nxt, L);
         if (s.cur_n) {
             depth = L + 1;
@@ -2490,7 +2682,7 @@ struct rmc_ctx {
     bool batch_ok() const {
         const Shard &s = sh[0];
         const uint64_t first = s.cur_n * (uint64_t)ks.maxsucc;
-        return !coverage && (!multi || (replicated && s.cur_n < shard_min)) && inited && !finished && cfg.device_levels != 1 &&
+        return !coverage && !graph && (!multi || (replicated && s.cur_n < shard_min)) && inited && !finished && cfg.device_levels != 1 &&
                s.cur_n > 0 && s.cur_n <= dev_parents() && ring_room(s, first * (uint64_t)ks.RECW_MAX, 0) &&
                seen_room(s, s.T_count + 2 * first);
     }
@@ -2820,6 +3012,9 @@ struct rmc_ctx {
         st->status = status;
         finished = true;
         build_trace();
+        // graph mode: the states below `distinct`, and the edges up to TLC's stopping point
+        if (graph)
+            graph_level(s, gid_cur, p + 1, gid_nxt, total_distinct - gid_nxt, p, (uint32_t)((ek >> 8) & 0xFFFF), kind);
     }
 
     // ---- sharded level (W > 1) ------------------------------------------------------------------
@@ -3947,6 +4142,7 @@ struct rmc_ctx {
         if (inited) throw Fail(RMC_E_STATE, "resume: needs a context not yet initialised (rmc_create or rmc_reset)");
         if (coverage)
             throw Fail(RMC_E_ARG, "resume: checkpoints do not carry action coverage (rmc_set_coverage is on)");
+        if (graph) throw Fail(RMC_E_ARG, "resume: checkpoints do not carry the gid map (rmc_set_graph is on)");
         if (cont)
             throw Fail(RMC_E_ARG, "resume: checkpoints do not carry the violation counts (rmc_set_continue is on)");
         try {
@@ -4160,6 +4356,10 @@ struct rmc_ctx {
         std::memset(cov_total, 0, sizeof cov_total);  // (the setting stays)
         std::memset(cov_level, 0, sizeof cov_level);
         viol_reset();  // (the setting stays)
+        if (gmap && graph) {  // (graph mode: the setting stays, the map is emptied; switched off, rmc_set_graph empties it)
+            HIPCHK(hipMemsetAsync(gmap, 0, gmap_cap * sizeof(GSlot), stream));
+            gmap_count = 0;
+        }
         violated = -1;
         err_ref = 0;
         err_last_slot = KEY_NONE;
@@ -4330,6 +4530,35 @@ int rmc_get_coverage(void *ctx, rmc_coverage *out) {
             out->distinct[k] = c->cov_total[16 + k];
         }
         out->init_generated = out->init_distinct = 1;
+        return RMC_OK;
+    });
+}
+
+int rmc_set_graph(void *ctx, const rmc_graph_sink *sink) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        if (c->inited) throw Fail(RMC_E_STATE, "rmc_set_graph: after rmc_create or rmc_reset, before rmc_init");
+        if (sink && (c->multi || c->W > 1 || c->cfg.world_size > 1 || c->cfg.virtual_shards > 1))
+            throw Fail(RMC_E_ARG, "rmc_set_graph: single GPU only (world_size and virtual_shards at most 1)");
+        if (sink && sink->map_log2 > 40) throw Fail(RMC_E_ARG, "rmc_set_graph: map_log2 above 40");
+        if (!sink) {  // off: nothing more is launched; what graph mode allocated stays with the context for a later
+                      // rmc_set_graph of the same sizes (rmc_destroy frees it)
+            c->graph = false;
+            c->gsink.user = nullptr;
+            c->gsink.states = nullptr;
+            c->gsink.edges = nullptr;
+            return RMC_OK;
+        }
+        if (c->gmap && (sink->map_log2 != c->gsink.map_log2 || sink->chunk_parents != c->gsink.chunk_parents)) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            c->graph_free();  // (rmc_init allocates for the new setting)
+        }
+        if (c->gmap && c->gmap_count) {  // (a map kept from before graph mode was switched off)
+            HIPCHK(hipMemsetAsync(c->gmap, 0, c->gmap_cap * sizeof(GSlot), c->stream));
+            c->gmap_count = 0;
+        }
+        c->graph = true;
+        c->gsink = *sink;
         return RMC_OK;
     });
 }

@@ -274,8 +274,36 @@ struct ViolParams {
     uint32_t iter;
 };
 
+// Graph mode (rmc_set_graph; TLC's -dump): the gid map -- open addressing over the full fingerprint {x | 1, y}
+// with the state's global id as the value, one 32-B sector per slot (x == 0: free), a power of two of slots
+// kept at load <= 1/2 by the host -- and the edge pass.  k_gid_insert fingerprints n committed records (P.front /
+// P.foff / P.fbase / P.rcap name them, as for k_viol_scan) and puts record i in with global id gid0 + i.
+// k_edges re-evaluates the parents [P.p_begin, P.p_end) of a launch, a wave each, in two passes: with off ==
+// nullptr it writes each parent's number of edges to cnt (chunk-local), with off (the exclusive scan of cnt) it
+// writes parent pl's edges at off[pl] + rank, rank in TLC order: the parent's global id, the successor's key in
+// rmc_successors' format, and the successor's global id from the map (a successor bit-equal to its parent: the
+// parent's, no fingerprint).  A lookup that misses sets *flag.  pos0 / bound_*: the cut at an error, as
+// CoverParams, but inside the erring parent an invariant or evaluation error keeps the edges up to and including
+// the erring successor (slot key <= bound_key), an Assert the sub-action batches before its own.
+struct GSlot { unsigned long long x, y, gid, pad; };
+struct GidMap {
+    GSlot *T;
+    uint64_t mask;  // slots - 1
+};
+struct EdgeParams {
+    GidMap map;
+    uint32_t *cnt;
+    const uint32_t *off;
+    unsigned long long *src, *dst;
+    uint32_t *key, *flag;
+    uint64_t pos0, bound_pos;
+    uint32_t bound_key, bound_kind;  // ErrSlot
+};
+
 struct KernelSet {
     int N, V, MR, MCAP, CCW, RECW_MAX, maxsucc;
+    void (*gid_insert)(const KParams &, uint64_t n, GidMap, uint64_t gid0, hipStream_t);  // graph mode: n records into the map
+    void (*edges)(const KParams &, const EdgeParams &, hipStream_t);                      // graph mode: count / write pass
     int ctxw;                                                 // hash-context words per parent (split chunks)
     void (*single)(const KParams &, hipStream_t);           // all successors of front[0] -> next, fp, out_keys
     void (*fused)(const KParams &, hipStream_t);            // expand + hash + probe + election + staging
@@ -348,6 +376,8 @@ void launch_owner_of(const ulonglong2 *fp, uint32_t W, uint32_t *out, hipStream_
 void launch_cover_new(const uint16_t *keys, uint32_t stride, uint64_t n, unsigned long long *dist, hipStream_t s);
 // ... dst[i] += src[i], src[i] = 0 for i < n <= 64 (a chunk's counters into its level's)
 void launch_cover_fold(unsigned long long *dst, unsigned long long *src, int n, hipStream_t s);
+// graph mode: every entry of a gid map into a larger one (cleared by the caller)
+void launch_gid_rehash(const GSlot *Told, uint64_t old_cap, GidMap dst, hipStream_t s);
 // out[i] = 1 if fp[i] is in `seen` -- for the fingerprints the shard `self` of W owns (W = 1: all)
 void launch_seen_query(const ulonglong2 *fp, uint64_t n, Seen seen, uint32_t W, uint32_t self, uint8_t *out,
                        hipStream_t s);

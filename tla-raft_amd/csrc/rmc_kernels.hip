@@ -4081,6 +4081,191 @@ __global__ __launch_bounds__(256) void k_viol_scan(KParams P, uint64_t n, ViolPa
     }
 }
 
+// ---- graph mode (rmc_set_graph; TLC's -dump) ---------------------------------------------------------
+// The gid map: the seen set stores fingerprints without ids, so the state graph's edges are resolved
+// through a table of its own, filled on the side of the search.  Slots are only ever filled (x by a CAS,
+// then y and the id by plain stores); inserts and lookups never share a launch, and every fingerprint is
+// inserted once, so an insert takes the first free slot of its run without comparing (two inserts racing
+// on equal x words, different states, just take two slots) and a lookup compares both words.
+__device__ __forceinline__ uint64_t g_index(const ulonglong2 f, uint64_t mask) {
+    return (f.x ^ (f.x >> 27) ^ (f.y >> 13)) & mask;
+}
+__device__ __forceinline__ void gid_put(const GidMap &G, ulonglong2 f, unsigned long long gid) {
+    uint64_t h = g_index(f, G.mask);
+    for (uint64_t tries = 0; tries <= G.mask; tries++) {  // (load <= 1/2: a free slot exists)
+        if (atomicCAS(&G.T[h].x, 0ull, (unsigned long long)f.x) == 0ull) {
+            G.T[h].y = f.y;
+            G.T[h].gid = gid;
+            return;
+        }
+        h = (h + 1) & G.mask;
+    }
+}
+// the state's global id, or all ones
+__device__ __forceinline__ unsigned long long gid_get(const GidMap &G, ulonglong2 f) {
+    uint64_t h = g_index(f, G.mask);
+    for (uint64_t tries = 0; tries <= G.mask; tries++) {
+        const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(&G.T[h]);
+        const ulonglong2 a = p[0], b = p[1];  // the slot's sector (plain C++: the compiler schedules the two loads)
+        if (a.x == 0ull) return ~0ull;
+        if (a.x == f.x && a.y == f.y) return b.x;
+        h = (h + 1) & G.mask;
+    }
+    return ~0ull;
+}
+
+// n committed records into the map, a wave per record (k_fp_states' device code), record i as gid0 + i
+template <int N, int V, int MR>
+__global__ __launch_bounds__(64) void k_gid_insert(KParams P, uint64_t n, GidMap G, uint64_t gid0) {
+    using S = Spec<N, V, MR>;
+    __shared__ uint64_t M0[N * N], M1[N * N];
+    __shared__ uint32_t pcore[Layout<N, V>::NW + N];
+    const int lane = threadIdx.x;
+    for (uint64_t p = blockIdx.x; p < n; p += gridDim.x) {
+        Wave<N, V, MR> W;
+        load_parent<N, V, MR, true>(P, rec_start<S::RECW_MAX>(P, p), lane, W, M0, M1, pcore);
+        const ulonglong2 f = fingerprint<N, V>(W.c, M0, M1, P.t);
+        if (lane == 0) gid_put(G, f, gid0 + p);
+        __syncthreads();  // the sums and the core in LDS are read out before the next record's go in
+    }
+}
+
+// The edges of the parents of a launch, a 64-lane wave per parent, grid-strided.  A parent is loaded and its
+// candidates are evaluated exactly as k_expand, k_walk and k_cover do, and ranked in TLC order as k_expand's
+// M_SINGLE mode ranks them for rmc_successors.  Count pass (Ep.off == nullptr): the parent's number of edges
+// under the cut.  Write pass: each successor in rank order is rebuilt as a record in LDS (write_record, as
+// k_walk does) and fingerprinted as a whole state (k_fp_states' device code) unless it is its parent bit for
+// bit; then the lanes look the parent's fingerprints up in the gid map together -- one random 32-B read each
+// -- and write its edges, consecutive in the three output arrays, a lane per edge.  No global atomics.
+template <int N, int V, int MR, bool BFV>
+__global__ __launch_bounds__(64) void k_edges(KParams P, EdgeParams Ep) {
+    using S = Spec<N, V, MR>;
+    using Lo = Layout<N, V>;
+    constexpr int NC = MR + 1 + (BFV ? MR : 0);        // candidates per lane: messages, slot, BecomeFollower
+    constexpr int MX = S::MAXS + (BFV ? S::MCAP : 0);  // successors per parent at most
+    __shared__ uint32_t pcore[Lo::NW + N], qcore[Lo::NW + N];
+    __shared__ uint64_t M0[N * N], M1[N * N];
+    __shared__ uint32_t srec[S::RECW_MAX];
+    __shared__ ulonglong2 sFp[MX];
+    __shared__ uint32_t sKey[MX];                      // slot key | 1 << 16: the parent itself
+    extern __shared__ uint32_t sBM[];                  // bitmap of the parent's message ids (P.t.bmw words)
+    const int lane = threadIdx.x;
+    KParams Pl = P;  // the successor's record in LDS: fixed stride, no ring
+    Pl.front = srec;
+    Pl.foff = nullptr;
+    Pl.rcap = ~0ull;
+    for (uint64_t p = P.p_begin + blockIdx.x; p < P.p_end; p += gridDim.x) {
+        const uint64_t pl = p - P.p_begin, pos = Ep.pos0 + pl;
+        uint32_t klim = KEY_NONE;  // the slot keys below it are edges
+        if (pos > Ep.bound_pos) klim = 0u;
+        else if (pos == Ep.bound_pos)
+            klim = Ep.bound_kind == ERR_DEADLOCK ? 0u : Ep.bound_kind == ERR_ASSERT ? (Ep.bound_key >> 7) << 7 : Ep.bound_key + 1u;
+        if (klim == 0u) {
+            if (!Ep.off && lane == 0) Ep.cnt[pl] = 0u;
+            continue;
+        }
+        Wave<N, V, MR> W;
+        load_parent<N, V, MR, false>(P, rec_start<S::RECW_MAX>(P, p), lane, W, nullptr, nullptr, pcore);
+        msg_bitmap<N, V, MR>(sBM, P.t.bmw, W, lane);
+        W.bm = sBM;
+        Succ<N, V, MR> cand[NC];
+        uint32_t akey = KEY_NONE;
+        int ln = lane;  // (opaque, as in k_expand: what the evaluation derives from it is not hoisted)
+        asm volatile("" : "+v"(ln));
+        uint32_t mid[MR], sid[N - 1];
+        {
+            uint32_t snat[N - 1];
+            slot_nats<N, V, MR>(P, W, ln, snat);
+#pragma unroll
+            for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
+#pragma unroll
+            for (int q = 0; q < N - 1; q++) sid[q] = nat_lookup(P, snat[q]);
+        }
+#pragma unroll
+        for (int r = 0; r < MR; r++)
+            eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey, nullptr, mid[r]);
+        eval_slot<N, V, MR>(P, W, ln, cand[MR], nullptr, sid);
+        // the cut takes a prefix of TLC's order: the ranks of what stays are those of the whole list
+        uint64_t en[NC];
+        uint32_t total = 0;
+#pragma unroll
+        for (int r = 0; r < NC; r++) {
+            if (cand[r].key >= klim) cand[r].key = KEY_NONE;
+            en[r] = __ballot(cand[r].key != KEY_NONE);
+            total += (uint32_t)__popcll(en[r]);
+        }
+        if (!Ep.off) {
+            if (lane == 0) Ep.cnt[pl] = total;
+            __syncthreads();  // the bitmap and the core in LDS are read out before the next parent's go in
+            continue;
+        }
+        uint32_t rank[NC];
+#pragma unroll
+        for (int r = 0; r < NC; r++) rank[r] = 0;
+#pragma unroll
+        for (int q = 0; q < NC; q++) {
+            for (uint64_t m = en[q]; m; m &= m - 1) {
+                const int t = __ffsll((unsigned long long)m) - 1;
+                const uint32_t kt = rdlane(cand[q].key, t);
+#pragma unroll
+                for (int r = 0; r < NC; r++) rank[r] += kt < cand[r].key ? 1u : 0u;
+            }
+        }
+        bool ovf = false;  // (the search stopped with RMC_E_CAPACITY before such a parent's level was committed)
+#pragma unroll
+        for (int r = 0; r < NC; r++) ovf |= cand[r].key != KEY_NONE && W.nm + cand[r].nadd > (uint32_t)S::MCAP;
+        if (__ballot(ovf) || total > (uint32_t)MX) {
+            if (lane == 0) atomicOr(Ep.flag, 2u);
+            total = 0;
+        }
+        for (uint32_t idx = 0; idx < total; idx++) {
+            // the one candidate of rank idx: each lane's own copy of it, then the lane that holds it
+            Succ<N, V, MR> ch = cand[MR];
+            bool hit = false;
+#pragma unroll
+            for (int r = 0; r < NC; r++) {
+                const bool h = cand[r].key != KEY_NONE && rank[r] == idx;
+                if (h) ch = cand[r];
+                hit |= h;
+            }
+            const uint64_t hm = __ballot(hit);
+            if (!hm) {  // (unreachable: the ranks are a permutation of 0 .. total - 1)
+                if (lane == 0) atomicOr(Ep.flag, 2u);
+                if (lane == 0) sKey[idx] = 1u << 16;
+                continue;
+            }
+            const int t = __ffsll((unsigned long long)hm) - 1;
+            const uint32_t key = rdlane(ch.key, t);
+            const bool self = rdlane(ch.self ? 1u : 0u, t) != 0u;
+            if (lane == 0) sKey[idx] = key | (self ? 1u << 16 : 0u);
+            if (self) continue;
+            write_record<N, V, MR>(W, ch, t, lane, srec);
+            __syncthreads();
+            Wave<N, V, MR> W2;
+            load_parent<N, V, MR, true>(Pl, 0, lane, W2, M0, M1, qcore);
+            const ulonglong2 f = fingerprint<N, V>(W2.c, M0, M1, P.t);
+            if (lane == 0) sFp[idx] = f;
+            __syncthreads();  // the record and the sums are read out before the next successor's go in
+        }
+        __syncthreads();
+        const unsigned long long src = P.gid_parent_base + p;
+        const uint64_t o = Ep.off[pl];
+        for (uint32_t i = (uint32_t)lane; i < total; i += 64u) {
+            const uint32_t k = sKey[i];
+            unsigned long long dst = src;
+            if (!(k >> 16)) {
+                dst = gid_get(Ep.map, sFp[i]);
+                if (dst == ~0ull) atomicOr(Ep.flag, 1u);
+            }
+            const uint32_t sk = k & 0xFFFFu;
+            Ep.src[o + i] = src;
+            Ep.key[o + i] = (key_server(sk) << 24) | (key_action(sk) << 16) | key_witness(sk);
+            Ep.dst[o + i] = dst;
+        }
+        __syncthreads();  // the parent's LDS is read out before the next parent's goes in
+    }
+}
+
 static inline unsigned grid_for(uint64_t n) {
     const uint64_t cap = 256ull * RMC_GRID_PER_CU;  // one-wave blocks per CU (default 32) on 256 CUs
     return (unsigned)(n < cap ? (n ? n : 1) : cap);
@@ -4178,6 +4363,12 @@ struct Launch {
         const uint64_t b = (n + 255) / 256;
         if (n) hipLaunchKernelGGL((k_viol_scan<N, V, MR>), dim3((unsigned)(b < 4096 ? b : 4096)), dim3(256), 0, s, P, n, vp);
     }
+    static void gid_insert(const KParams &P, uint64_t n, GidMap g, uint64_t gid0, hipStream_t s) {
+        if (n) hipLaunchKernelGGL((k_gid_insert<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n, g, gid0);
+    }
+    static void edges(const KParams &P, const EdgeParams &ep, hipStream_t s) {
+        hipLaunchKernelGGL((k_edges<N, V, MR, BFV>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64), bm_bytes(P), s, P, ep);
+    }
     static void fps(const KParams &P, uint64_t n, hipStream_t s) {
         hipLaunchKernelGGL((k_fp_states<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n);
     }
@@ -4207,6 +4398,8 @@ static void fill(KernelSet *ks) {
     ks->walk = &Launch<N, V, MR, BFV>::walk;
     ks->cover = &Launch<N, V, MR, BFV>::cover;
     ks->viol_scan = &Launch<N, V, MR>::viol;
+    ks->gid_insert = &Launch<N, V, MR>::gid_insert;
+    ks->edges = &Launch<N, V, MR, BFV>::edges;
     ks->fp_states = &Launch<N, V, MR>::fps;
     ks->inv_states = &Launch<N, V, MR>::invs;
     ks->encode = &Launch<N, V, MR>::enc;
@@ -4515,6 +4708,16 @@ __global__ __launch_bounds__(256) void k_seen_query(const ulonglong2 *__restrict
 void launch_seen_query(const ulonglong2 *fp, uint64_t n, Seen seen, uint32_t W, uint32_t self, uint8_t *out,
                        hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_seen_query, dim3(grid256(n)), dim3(256), 0, s, fp, n, seen, W, self, out);
+}
+// graph mode: the gid map grown -- every entry of the old table into the new one
+__global__ __launch_bounds__(256) void k_gid_rehash(const GSlot *__restrict__ Told, uint64_t old_cap, GidMap dst) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_cap; i += (uint64_t)gridDim.x * blockDim.x) {
+        const GSlot e = Told[i];
+        if (e.x) gid_put(dst, make_ulonglong2(e.x, e.y), e.gid);
+    }
+}
+void launch_gid_rehash(const GSlot *Told, uint64_t old_cap, GidMap dst, hipStream_t s) {
+    hipLaunchKernelGGL(k_gid_rehash, dim3(grid256(old_cap)), dim3(256), 0, s, Told, old_cap, dst);
 }
 void launch_owner_of(const ulonglong2 *fp, uint32_t W, uint32_t *out, hipStream_t s) {
     hipLaunchKernelGGL(k_owner_of, dim3(1), dim3(64), 0, s, fp, W, out);

@@ -3,6 +3,7 @@
 //   raftmc [-deadlock] [-workers N] [-config Raft.cfg] [-device D] [-gpus N] [-msgcap C] [-seenlog2 K] Raft.tla
 //   raftmc -coverage MIN ... Raft.tla   (TLC's -coverage: the per-action distinct:generated report at the end)
 //   raftmc -continue ... Raft.tla       (TLC's -continue: search past invariant violations, count them per invariant)
+//   raftmc -dump FILE | -dump dot[,actionlabels] FILE ... Raft.tla   (TLC's -dump: the state graph, FILE.dump / FILE.dot)
 //   raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config Raft.cfg] [-device D] [-msgcap C] Raft.tla
 //
 // Accepts the flags myrun.sh passes to TLC (myrun.sh:3), reads the same Raft.tla /
@@ -17,6 +18,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <functional>
 #include <cstdio>
@@ -220,16 +222,97 @@ struct Printer {
     }
 };
 
+// -dump FILE / -dump dot[,actionlabels] FILE: the sink of rmc_set_graph.  States and edges arrive level by level;
+// the dump file takes the states as they come, the dot file its node lines, while the edge lines wait in a
+// temporary file and follow the last node (finish).  Both streams are buffered; a failed write makes the callback
+// return non-zero, which fails the step (RMC_E_SINK).
+struct DumpSink {
+    std::string path, err;
+    bool dot = false, labels = false;
+    FILE *f = nullptr, *ef = nullptr;  // the file; dot: the edge lines so far
+    const Printer *pr = nullptr;
+    bool fail(const char *what) {
+        if (err.empty()) err = std::string(what) + " " + path + ": " + std::strerror(errno);
+        return false;
+    }
+    bool open() {
+        f = std::fopen(path.c_str(), "w");
+        if (!f) return fail("cannot open");
+        if (!dot) return true;
+        ef = std::tmpfile();
+        if (!ef) return fail("cannot create the temporary edge file of");
+        if (std::fputs("strict digraph DiskGraph {\nnodesep=0.35;\nsubgraph cluster_graph {\ncolor=\"white\";\n", f) < 0)
+            return fail("cannot write");
+        return true;
+    }
+    static std::string escape(const std::string &s) {  // a state as a dot label: no trailing newline
+        std::string o;
+        const size_t n = !s.empty() && s.back() == '\n' ? s.size() - 1 : s.size();
+        for (size_t i = 0; i < n; i++) {
+            if (s[i] == '\n') o += "\\n";
+            else if (s[i] == '"') o += "\\\"";
+            else if (s[i] == '\\') o += "\\\\";
+            else o += s[i];
+        }
+        return o;
+    }
+    static int32_t on_states(void *user, uint64_t gid0, uint64_t n, const int32_t *u, size_t stride) {
+        DumpSink *d = static_cast<DumpSink *>(user);
+        for (uint64_t i = 0; i < n; i++) {
+            const std::string st = d->pr->state(u + i * stride);
+            const unsigned long long num = (unsigned long long)(gid0 + i + 1);
+            const int rc = d->dot ? std::fprintf(d->f, "%llu [label=\"%s\"%s]\n", num, escape(st).c_str(),
+                                                 gid0 + i == 0 ? ",style = filled" : "")
+                                  : std::fprintf(d->f, "State %llu:\n%s\n", num, st.c_str());
+            if (rc < 0) return d->fail("cannot write") ? 0 : 1;
+        }
+        return 0;
+    }
+    static int32_t on_edges(void *user, uint64_t n, const uint64_t *src, const uint32_t *key, const uint64_t *dst) {
+        DumpSink *d = static_cast<DumpSink *>(user);
+        if (!d->dot) return 0;
+        for (uint64_t i = 0; i < n; i++) {
+            const uint32_t a = (key[i] >> 16) & 0xFFu;
+            if (std::fprintf(d->ef, "%llu -> %llu [label=\"%s\",color=\"black\",fontcolor=\"black\"];\n",
+                             (unsigned long long)(src[i] + 1), (unsigned long long)(dst[i] + 1),
+                             d->labels && a < 13 ? kActionNames[a] : "") < 0)
+                return d->fail("cannot write the temporary edge file of") ? 0 : 1;
+        }
+        return 0;
+    }
+    // the edge lines behind the nodes, the closing braces, and the file closed
+    bool finish() {
+        if (!f) return err.empty();
+        if (dot) {
+            char buf[1 << 16];
+            if (std::fflush(ef) != 0 || std::fseek(ef, 0, SEEK_SET) != 0) return fail("cannot read back the edges of");
+            for (size_t k; (k = std::fread(buf, 1, sizeof buf, ef)) > 0;)
+                if (std::fwrite(buf, 1, k, f) != k) return fail("cannot write");
+            if (std::ferror(ef)) return fail("cannot read back the edges of");
+            if (std::fputs("}\n}\n", f) < 0) return fail("cannot write");
+            std::fclose(ef);
+            ef = nullptr;
+        }
+        FILE *g = f;
+        f = nullptr;
+        if (std::fclose(g) != 0) return fail("cannot write");
+        return true;
+    }
+};
+
 int usage(const char *msg) {
     std::fprintf(stderr, "raftmc: %s\nusage: raftmc [-deadlock] [-workers N] [-config FILE.cfg] [-device D] "
                          "[-gpus N [-onerank] [-shardmin K]] [-msgcap C] [-seenlog2 K] [-checkpoint MIN] [-metadir DIR] "
-                         "[-recover DIR] [-coverage MIN] [-continue] FILE.tla\n"
+                         "[-recover DIR] [-coverage MIN] [-continue] [-dump [dot[,actionlabels]] FILE] FILE.tla\n"
                          "       raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config FILE.cfg] [-device D] "
                          "[-msgcap C] FILE.tla\n"
                          "  -coverage MIN  per-action coverage (distinct:generated) at the end of the search; the interval "
                          "is parsed as TLC's, only the final report is printed\n"
                          "  -continue  search past invariant violations: per violated invariant the first behaviour and the "
                          "number of violating states (TLC prints every one); exit code 12 if any\n"
+                         "  -dump FILE  every distinct state in discovery order to FILE.dump; -dump dot FILE: the state graph "
+                         "(states and every edge) to FILE.dot, with dot,actionlabels the edges carry their action's name; "
+                         "one GPU, not with -simulate or -recover\n"
                          "  -simulate  random behaviours instead of the breadth-first search; num=N of them (default "
                          "1000000; TLC's default is unbounded)\n"
                          "  -depth D   states per behaviour at most (default 100, as TLC)\n"
@@ -429,6 +512,8 @@ int main(int argc, char **argv) {
     long long sim_depth = 100;                           // TLC -depth
     bool coverage = false, cov_bad = false;              // TLC -coverage <minutes>
     bool cont = false;                                   // TLC -continue
+    bool dump = false, dump_dot = false, dump_labels = false;  // TLC -dump [dot[,options]] FILE
+    std::string dump_file, dump_bad;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *f) -> const char * {
@@ -460,6 +545,20 @@ int main(int argc, char **argv) {
             if (i + 1 >= argc || !isdigit((unsigned char)argv[i + 1][0])) cov_bad = true;
             else if (std::strtod(argv[++i], &end), *end) cov_bad = true;
         } else if (a == "-continue") cont = true;
+        else if (a == "-dump") {
+            dump = true;
+            std::string v = need("-dump");
+            if (v == "dot" || v.compare(0, 4, "dot,") == 0) {  // the format and its options, then the file
+                dump_dot = true;
+                std::stringstream opts(v.size() > 4 ? v.substr(4) : std::string());
+                for (std::string o; std::getline(opts, o, ',');) {
+                    if (o == "actionlabels") dump_labels = true;
+                    else dump_bad += (dump_bad.empty() ? "" : ", ") + o;
+                }
+                v = need("-dump dot");
+            }
+            dump_file = v;
+        }
         else if (a == "-depth") sim_depth = std::atoll(need("-depth"));
         else if (a == "-seed") { sim_seed = (unsigned long long)std::strtoll(need("-seed"), nullptr, 10); seed_given = true; }
         else if (a == "-metadir") metadir = need("-metadir");
@@ -478,6 +577,16 @@ int main(int argc, char **argv) {
     if (cont) {  // refused before anything touches a device
         if (simulate) return usage("-continue cannot be combined with -simulate");
         if (!recover_dir.empty()) return usage("-continue cannot be combined with -recover (checkpoints do not carry the violation counts)");
+    }
+    if (dump) {  // refused before anything touches a device
+        if (!dump_bad.empty()) return usage(("-dump dot supports only the actionlabels option, not " + dump_bad).c_str());
+        if (dump_file.empty() || dump_file[0] == '-') return usage("-dump takes a file name");
+        if (simulate) return usage("-dump cannot be combined with -simulate");
+        if (!recover_dir.empty()) return usage("-dump cannot be combined with -recover (checkpoints do not carry the state graph)");
+        if (gpus > 1 || onerank) return usage("-dump runs on one GPU (no -gpus)");
+        const std::string ext = dump_dot ? ".dot" : ".dump";  // (TLC appends the extension unless it is there)
+        if (dump_file.size() < ext.size() || dump_file.compare(dump_file.size() - ext.size(), ext.size(), ext) != 0)
+            dump_file += ext;
     }
     if (simulate) {  // refused before anything touches a device
         if (sim_bad) return usage("-simulate takes num=N with N >= 1");
@@ -627,6 +736,28 @@ int main(int argc, char **argv) {
         rmc_destroy(ctx);
         return 75;
     }
+    DumpSink ds;
+    const Printer dump_pr{pm, cfg.n_servers, cfg.n_vals};
+    if (dump) {
+        ds.path = dump_file;
+        ds.dot = dump_dot;
+        ds.labels = dump_labels;
+        ds.pr = &dump_pr;
+        rmc_graph_sink gs{};
+        gs.user = &ds;
+        gs.states = &DumpSink::on_states;
+        gs.edges = &DumpSink::on_edges;
+        if (!ds.open()) {
+            std::printf("Error: %s\n", ds.err.c_str());
+            rmc_destroy(ctx);
+            return 75;
+        }
+        if (rmc_set_graph(ctx, &gs) < 0) {
+            std::printf("Error: %s\n", rmc_last_error(ctx));
+            rmc_destroy(ctx);
+            return 75;
+        }
+    }
     if (!recover_dir.empty()) {
         // TLC -recover: carry on from the checkpoint in that directory (rmc_resume)
         const std::string f = recover_dir + "/raftmc.ckpt";
@@ -642,7 +773,11 @@ int main(int argc, char **argv) {
     } else {
         std::printf("Computing initial states...\n");
         rc = rmc_init(ctx, &st);
-        if (rc < 0) { std::printf("Error: %s\n", rmc_last_error(ctx)); rmc_destroy(ctx); return 75; }
+        if (rc < 0) {
+            std::printf("Error: %s\n", !ds.err.empty() ? ds.err.c_str() : rmc_last_error(ctx));
+            rmc_destroy(ctx);
+            return 75;
+        }
         std::printf("Finished computing initial states: 1 distinct state generated at %s.\n", now_str().c_str());
     }
     if (metadir.empty()) metadir = "states/" + stamp_str();
@@ -672,7 +807,9 @@ int main(int argc, char **argv) {
         last = lv[nl - 1];
         have_last = true;
         const auto now = std::chrono::steady_clock::now();
-        if (!reported || std::chrono::duration<double>(now - last_progress).count() >= progress_s) {
+        // (-dump runs a level per call where the plain run's first call covers a device-driven batch of them: its
+        // first report waits for the interval or the closing one, so both runs print the same lines)
+        if ((!reported && !dump) || std::chrono::duration<double>(now - last_progress).count() >= progress_s) {
             progress(last);
             reported = true;
             printed_level = last.level;
@@ -692,7 +829,12 @@ int main(int argc, char **argv) {
         }
     }
     if (rc < 0) {
-        std::printf("Error: %s\n", rmc_last_error(ctx));
+        std::printf("Error: %s\n", !ds.err.empty() ? ds.err.c_str() : rmc_last_error(ctx));
+        rmc_destroy(ctx);
+        return 75;
+    }
+    if (dump && !ds.finish()) {
+        std::printf("Error: %s\n", ds.err.c_str());
         rmc_destroy(ctx);
         return 75;
     }

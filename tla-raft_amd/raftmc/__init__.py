@@ -22,7 +22,7 @@ RMC_OK, RMC_DONE, RMC_VIOLATION, RMC_ASSERT, RMC_EVAL_ERROR, RMC_DEADLOCK = 0, 1
 STATUS_NAMES = {RMC_OK: "ok", RMC_DONE: "done", RMC_VIOLATION: "invariant", RMC_ASSERT: "assert",
                 RMC_EVAL_ERROR: "eval_error", RMC_DEADLOCK: "deadlock"}
 ERRORS = {-1: "RMC_E_ARG", -2: "RMC_E_DEVICE", -3: "RMC_E_MEMORY", -4: "RMC_E_CAPACITY",
-          -5: "RMC_E_STATE", -6: "RMC_E_PARSE", -7: "RMC_E_COMM"}
+          -5: "RMC_E_STATE", -6: "RMC_E_PARSE", -7: "RMC_E_COMM", -8: "RMC_E_SINK"}
 
 # invariant bits (include/rmc.h), Raft.tla:434-503
 INVARIANT_BITS = {
@@ -114,6 +114,17 @@ class _Transport(ctypes.Structure):
                 ("alltoallv", _ALLTOALLV)]
 
 
+_I32P = ctypes.POINTER(ctypes.c_int32)
+_U32P = ctypes.POINTER(ctypes.c_uint32)
+_GRAPH_STATES = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _I32P, ctypes.c_size_t)
+_GRAPH_EDGES = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, _U64P, _U32P, _U64P)
+
+
+class _GraphSink(ctypes.Structure):
+    _fields_ = [("user", ctypes.c_void_p), ("states", _GRAPH_STATES), ("edges", _GRAPH_EDGES),
+                ("chunk_parents", ctypes.c_uint32), ("map_log2", ctypes.c_uint32)]
+
+
 _lib = None
 
 
@@ -170,6 +181,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.rmc_get_violations.argtypes = [vp, P(_Violations)]
         lib.rmc_get_violation_levels.argtypes = [vp, u32, P(u64), u32, P(u32)]
         lib.rmc_violation_trace.argtypes = [vp, u32]
+    if hasattr(lib, "rmc_set_graph"):  # (likewise)
+        lib.rmc_set_graph.argtypes = [vp, P(_GraphSink)]
     _lib = lib
     return lib
 
@@ -728,6 +741,78 @@ class ModelChecker:
         becomes the current trace)."""
         self._check(self.lib.rmc_violation_trace(self.h, self._inv_bit(name)))
         return self.trace()
+
+    def set_graph(self, states: bool = True, chunk_parents: int = 0, map_log2: int = 0, on_states=None,
+                  on_edges=None) -> None:
+        """TLC's -dump: stream the state graph of the run (include/rmc.h rmc_set_graph).  On a fresh or
+        reset checker, before init() / run().  Without callbacks the binding collects: graph_edges() and
+        graph_states() return what has been delivered so far.  on_states(gid0, unpacked) gets a numpy int32
+        array of shape (n, stride) and on_edges(src, key, dst) three numpy arrays (u64, u32, u64), all views
+        valid only during the call; a callback that raises or returns a true value fails the step with
+        RMC_E_SINK.  states=False: the states are not copied back."""
+        import numpy as np
+        if not hasattr(self.lib, "rmc_set_graph"):
+            raise RmcError("this librmc.so has no graph mode (rmc_set_graph): rebuild it")
+        self._g_src, self._g_key, self._g_dst, self._g_states = [], [], [], []
+
+        def failed():
+            import sys
+            import traceback
+            traceback.print_exc(file=sys.stderr)
+            return 1
+
+        def c_states(_user, gid0, n, unpacked, stride):
+            try:
+                a = np.ctypeslib.as_array(unpacked, shape=(n, stride))
+                if on_states is not None:
+                    return 1 if on_states(gid0, a) else 0
+                self._g_states.append(a.copy())
+                return 0
+            except Exception:  # noqa: BLE001 -- the library raises RMC_E_SINK
+                return failed()
+
+        def c_edges(_user, n, src, key, dst):
+            try:
+                s, k, d = (np.ctypeslib.as_array(p, shape=(n,)) for p in (src, key, dst))
+                if on_edges is not None:
+                    return 1 if on_edges(s, k, d) else 0
+                self._g_src.append(s.copy())
+                self._g_key.append(k.copy())
+                self._g_dst.append(d.copy())
+                return 0
+            except Exception:  # noqa: BLE001
+                return failed()
+
+        # (the callback objects live as long as the checker: the library calls them from every step)
+        self._g_sink = _GraphSink(None, _GRAPH_STATES(c_states) if states else _GRAPH_STATES(), _GRAPH_EDGES(c_edges),
+                                  chunk_parents, map_log2)
+        self._g_on = False
+        self._check(self.lib.rmc_set_graph(self.h, ctypes.byref(self._g_sink)))
+        self._g_on = True
+
+    def clear_graph(self) -> None:
+        """Graph mode off (on a fresh or reset checker); what was collected is dropped."""
+        if getattr(self, "_g_on", False):
+            self._g_on = False
+            self._check(self.lib.rmc_set_graph(self.h, None))
+
+    def _graph_check(self):
+        if not getattr(self, "_g_on", False):
+            raise RmcError("RMC_E_STATE: graph mode is off (set_graph)")
+
+    def graph_edges(self):
+        """(src u64, key u32, dst u64) numpy arrays of the edges delivered so far, in TLC -workers 1 order;
+        key = server << 24 | action << 16 | witness."""
+        import numpy as np
+        self._graph_check()
+        cat = lambda parts, t: np.concatenate(parts) if parts else np.zeros(0, dtype=t)  # noqa: E731
+        return cat(self._g_src, np.uint64), cat(self._g_key, np.uint32), cat(self._g_dst, np.uint64)
+
+    def graph_states(self) -> List[dict]:
+        """The states delivered so far in global-id order (Init first), as unpacked_to_state dicts."""
+        self._graph_check()
+        n, V = self.cfg.n_servers, self.cfg.n_vals
+        return [unpacked_to_state(row.tolist(), n, V) for part in self._g_states for row in part]
 
     def trace(self) -> List[Tuple[Optional[Tuple[int, int, int]], dict]]:
         n = ctypes.c_uint32()
