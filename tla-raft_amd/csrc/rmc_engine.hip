@@ -970,6 +970,32 @@ struct rmc_ctx {
     const uint32_t probe_run = (uint32_t)env_int("RMC_PROBE_RUN", 0, 0, 64);
     const int probe_log = env_int("RMC_PROBE_DEDUP_LOG", 0, 0, 1);
 
+    // ---- grids of a single-GPU split chunk's expansion and items commit -------------------------------
+    // Both kernels' blocks stride over batches of 64 parents, so the grid is a whole number of resident
+    // generations: a generation is the blocks of the instantiation a CU holds (KernelSet::items_blocks, asked
+    // once here) on the device's CUs, and the grid the fewest generations that make ITEMS_MIN_BLOCKS blocks; a
+    // launch takes min(batches, grid) blocks and every block ceil(batches / grid) batches or one fewer.
+    // ITEMS_MIN_BLOCKS is the fixed grid these kernels ran at before: two generations at four blocks per CU on
+    // 256 CUs, but one and three fifths at five -- a last generation that leaves two fifths of the CUs' slots
+    // empty cost the five-wave commit 0.42 s per Raft.cfg exhaustion, and a single generation (every block
+    // resident from the start, beside the other stream's kernels) was up to 0.8 s slower than two and erratic
+    // from run to run (profiles/ab_items_residency.txt).
+    // RMC_ITEMS_GRID (read once): 0 or unset = that grid; N = exactly N blocks at most, for both kernels
+    // (tests: the stride loop on small chunks; A/B runs of other grids).
+    static constexpr unsigned ITEMS_MIN_BLOCKS = 2048;
+    const int items_grid_env = env_int("RMC_ITEMS_GRID", 0, 0, 1 << 20);
+    unsigned items_xgrid = 0, items_cgrid = 0;
+    void size_items_grids(int cus) {
+        int xb = 0, cb = 0;
+        HIPCHK(ks.items_blocks(&xb, &cb));
+        auto whole = [&](int per_cu) {
+            const unsigned gen = (unsigned)(per_cu * cus);
+            return gen ? (ITEMS_MIN_BLOCKS + gen - 1) / gen * gen : 0u;
+        };
+        items_xgrid = items_grid_env ? (unsigned)items_grid_env : whole(xb);
+        items_cgrid = items_grid_env ? (unsigned)items_grid_env : whole(cb);
+    }
+
     // the other set becomes the one the Shard's members (and so base / chunk_params, error_counts)
     // name, with the events of the expansion that filled it
     void swap_staging(Shard &s) {
@@ -1248,6 +1274,7 @@ struct rmc_ctx {
         HIPCHK(hipGetDeviceProperties(&prop, dev));
         if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
             throw Fail(RMC_E_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950");
+        size_items_grids(prop.multiProcessorCount);
         // (all three streams at the default priority: the main stream at a higher one than the expansion
         // stream measured 9 % slower)
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -2517,7 +2544,7 @@ struct rmc_ctx {
             if (!expanded) {
                 HIPCHK(hipMemsetAsync(s.sum + SUM_SELF, 0, SUM_CLEAR, stream));
                 timed(PH_HASH, [&] {
-                    if (split) ks.split(params(), stream);
+                    if (split) ks.split(params(), items_xgrid, stream);
                     else ks.fused(params(), stream);
                 });
             }
@@ -2549,7 +2576,7 @@ struct rmc_ctx {
                 HIPCHK(hipMemsetAsync(s.alt.sum + SUM_SELF, 0, SUM_CLEAR, xstream));
                 s.alt.timed = time_hash;
                 if (time_hash) HIPCHK(hipEventRecord(s.alt.t0, xstream));
-                ks.split(Q, xstream);
+                ks.split(Q, items_xgrid, xstream);
                 if (time_hash) HIPCHK(hipEventRecord(s.alt.t1, xstream));
                 HIPCHK(hipEventRecord(s.alt.done, xstream));
                 ahead = true;
@@ -2586,7 +2613,7 @@ struct rmc_ctx {
             if (split && !fold) timed(PH_DEDUP, [&] { ks.insert(params(), np_, stream); });
             // + chunk summary; a split chunk's winners a lane per successor slot of its parents with winners
             timed(PH_MAT, [&] {
-                if (split) ks.commit_split(params(), np_, stream);
+                if (split) ks.commit_split(params(), np_, items_cgrid, stream);
                 else ks.commit(params(), stream);
             });
             HIPCHK(hipMemcpyAsync(s.hsum, s.sum, (SUM_PDROP + 1) * 8, hipMemcpyDeviceToHost, stream));
@@ -3196,7 +3223,7 @@ struct rmc_ctx {
                             Q.self = (uint32_t)s.id;
                             Q.gblk = s.gblk;
                         }
-                        ks.split(Q, stream);
+                        ks.split(Q, 0, stream);
                         ks.hash_probe(Q, s.np, stream);
                     } else {
                         ks.fused(Q, stream);
@@ -3367,7 +3394,7 @@ struct rmc_ctx {
                                         // (by k_commit_items; k_local_flags has left verdicts where k_commit_split runs)
                             Q.OT = s.rt_table;
                             Q.ot_round = s.rt_round;
-                            ks.commit_split(Q, s.np, stream);
+                            ks.commit_split(Q, s.np, 0, stream);
                         } else {
                             ks.commit(Q, stream);
                         }

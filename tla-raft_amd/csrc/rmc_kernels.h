@@ -307,15 +307,20 @@ struct KernelSet {
     int ctxw;                                                 // hash-context words per parent (split chunks)
     void (*single)(const KParams &, hipStream_t);           // all successors of front[0] -> next, fp, out_keys
     void (*fused)(const KParams &, hipStream_t);            // expand + hash + probe + election + staging
-    void (*split)(const KParams &, hipStream_t);            // split chunk: expand + staging + hash context
+    // split chunk: expand + staging + hash context, on at most `grid` blocks (whole resident generations, sized
+    // by the engine from items_blocks; 0: a sharded round's fixed 2048)
+    void (*split)(const KParams &, unsigned grid, hipStream_t);
+    // blocks per CU that stay resident of the split expansion and of the items commit of commit_split (0 where
+    // k_commit_split commits): the runtime's occupancy answer under the hardware's residency rule
+    hipError_t (*items_blocks)(int *expand, int *commit);
     void (*hash_probe)(const KParams &, uint64_t np, hipStream_t);  // split chunk: fingerprint + seen set + election
                                                                    // per successor (P.route: fingerprint only)
     void (*insert)(const KParams &, uint64_t np, hipStream_t);    // split chunk: winners into the seen set
     void (*wincount)(const KParams &, uint64_t np, hipStream_t);  // winners per parent + their scan, successors generated
     void (*commit)(const KParams &, hipStream_t);           // winners -> next level, seen set, trace, invariants;
                                                             // chunk summary (and the device loop's next level)
-    void (*commit_split)(const KParams &, uint64_t np, hipStream_t);  // ... a lane per successor slot of the parents
-                                                            // with winners (plist; LS_WIN verdicts) + summary
+    // ... a lane per successor slot of the parents with winners (plist; LS_WIN verdicts) + summary; grid: as split's
+    void (*commit_split)(const KParams &, uint64_t np, unsigned grid, hipStream_t);
     // sharded round, the successors the shard owns itself: bids in the round's owner table, then
     // (every bid in) verdicts in lslot, winners into the seen set and onto wacc
     void (*local_elect)(const KParams &, uint64_t np, Seen, ESlot *OT, uint64_t mask,

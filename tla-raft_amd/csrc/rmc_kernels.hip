@@ -24,6 +24,7 @@
 //   FUSED        single-GPU level: expand + fingerprint + seen-set probe + election + staging
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 
 #include "rmc_kernels.h"
 
@@ -2120,9 +2121,20 @@ __device__ __forceinline__ uint32_t slot_range(uint32_t role, uint32_t ec, uint3
     return bc << 4;
 }
 
-#ifndef RMC_ITEMS_WAVES  // waves per SIMD the item-parallel expansion's registers are cut for (0: the compiler's)
-#define RMC_ITEMS_WAVES 0
+// Waves per SIMD the split (item-parallel, FUSE = false) expansion's registers are cut for; 0: the compiler's
+// choice.  Five blocks of 256 threads per CU need <= 96 VGPRs and <= 32,768 B of LDS each; an instantiation is
+// cut to five only where the compiler's resource report (profiles/items_residency_resources.txt) shows that
+// bound honoured with no VGPR spill and no scratch.  A bound the LDS cannot follow is dropped by the backend
+// without a word (six waves here: 6 x 31 KB > 160 KB), so read the report before timing one.
+// -DRMC_ITEMS_WAVES=W (tools/build_variant.sh iw<W>) overrides the table for every instantiation, 0 included.
+template <int N, int V, int MR, bool BFV>
+constexpr int items_waves() {
+#ifdef RMC_ITEMS_WAVES
+    return RMC_ITEMS_WAVES;
+#else
+    return (MR == 1 && !(BFV && N == 3 && V >= 2)) ? 5 : 0;
 #endif
+}
 // Item classes: the action an item can take, from its message and its server's term and role alone
 // (the first guards of eval_msg / eval_slot) -- a round's items are evaluated class by class, so the
 // lanes of a wave take one action's branch, and messages no action can receive (an older term than
@@ -2156,7 +2168,7 @@ __device__ __forceinline__ uint32_t slot_class(uint32_t t) {
 // the message-parent notes that build gave wrong BecomeFollower n3 counts while the uncut one matches the oracle --
 // profiles/r06_ab_message_parents.txt)
 template <int N, int V, int MR, bool BFV, bool FUSE, int PB>
-__global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 && !BFV) ? RMC_FUSED_WAVES : 0) : RMC_ITEMS_WAVES) void k_expand_items(KParams P) {
+__global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 && !BFV) ? RMC_FUSED_WAVES : 0) : (items_waves<N, V, MR, BFV>())) void k_expand_items(KParams P) {
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
     constexpr int NT = items_threads<N, V, MR, FUSE>();
@@ -3505,8 +3517,24 @@ __device__ __forceinline__ void block_count_add(uint32_t mine, unsigned long lon
 // FUSE: a fused level's commit (device loop, chunks below the split size; k_commit's outputs): PB
 // consecutive parents at a time, those without winners skipped, the level from the control block, and
 // the last block to arrive finishes the level (finish_level).
-template <int N, int V, int MR, int MX, bool FUSE, int PB>
-__global__ __launch_bounds__(XB_THREADS) void k_commit_items(KParams P) {
+// Waves per SIMD the split chunks' commit is cut for, per instantiation from the resource report as
+// items_waves.  ROUTE: a sharded round's commit (P.route), split from the single-GPU chunk's at compile time --
+// neither carries the other's owner table / sidecar or election table / trace / seen set, which is what
+// brings the single-GPU n = 3 commits from 103-105 VGPRs to 96 at five waves with no VGPR spilled (the
+// sharded ones would spill 2; the n = 2 commits are below 96 at the compiler's choice; BecomeFollower's and
+// msg_cap 128's LDS is past 32,768 B).  The 8 B of private segment the n >= 3 commits declare is the frame
+// of the out-of-line NoAllCommit check (inv_nac), as before; the kernel's own code touches no scratch.
+// -DRMC_COMMIT_ITEMS_WAVES=W (tools/build_variant.sh cw<W>) overrides, 0 = the compiler's choice everywhere.
+template <int N, int V, int MR, int MX, bool FUSE, bool ROUTE>
+constexpr int commit_items_waves() {
+#ifdef RMC_COMMIT_ITEMS_WAVES
+    return FUSE ? 0 : RMC_COMMIT_ITEMS_WAVES;
+#else
+    return (!FUSE && !ROUTE && N == 3 && MR == 1 && MX <= 128) ? 5 : 0;
+#endif
+}
+template <int N, int V, int MR, int MX, bool FUSE, int PB, bool ROUTE = false>
+__global__ __launch_bounds__(XB_THREADS, (commit_items_waves<N, V, MR, MX, FUSE, ROUTE>())) void k_commit_items(KParams P) {
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
     constexpr int NT = XB_THREADS, CCW = S::CCW, RECW = S::RECW_MAX, SW4 = S::SW4;
@@ -3528,6 +3556,7 @@ __global__ __launch_bounds__(XB_THREADS) void k_commit_items(KParams P) {
     __shared__ uint8_t sWj[FUSE ? 1 : PB * RECW];  // per record word of the batch: its parent
     __shared__ uint8_t sSj[FUSE ? 1 : PB * MX];    // per successor slot of the batch: its parent
     const int tid = threadIdx.x;
+    const bool route = FUSE ? P.route != 0 : ROUTE;  // (a fused level's commit is never launched on a sharded round)
     uint32_t own_ins = 0;  // a split sharded round: its own winners this thread put into the seen set
     if constexpr (FUSE) {
 #ifdef RMC_RACE_PROBE
@@ -3624,9 +3653,9 @@ __global__ __launch_bounds__(XB_THREADS) void k_commit_items(KParams P) {
                 // the verdict (LS_WIN: k_insert_winners', an owner's), or -- no insert pass -- the election word; a
                 // split sharded round's own candidates (their slot in the round's owner table) are decided here
                 const uint32_t g = P.lslot[sq];
-                const bool own = P.route && P.OT && g < LS_WIN;  // (a table slot; LS_WIN < LS_ELECT < LS_SEEN)
+                const bool own = route && P.OT && g < LS_WIN;  // (a table slot; LS_WIN < LS_ELECT < LS_SEEN)
                 const bool win = own ? owner_same(P.OT[g].k, owner_key(P.ot_round + 1u, owner_order(P.gblk + sPl[j], r, 0u)))
-                               : (P.route || (P.split & 4)) ? g == LS_WIN
+                               : (route || (P.split & 4)) ? g == LS_WIN
                                                             : (g < LS_ELECT && elect_q(P.ET[g].k) == (uint32_t)q);
                 if (own) P.lslot[sq] = win ? LS_WIN : LS_SEEN;  // (the verdict, as k_local_flags leaves it: error counts)
                 if (win) {
@@ -3666,7 +3695,7 @@ __global__ __launch_bounds__(XB_THREADS) void k_commit_items(KParams P) {
                 const uint32_t pl = sPl[j];
                 const uint64_t p = P.p_begin + pl;
                 const uint64_t out = P.next_base + sOut[j] + ord;
-                if ((!P.route && !(P.split & 2)) || (e & 0x10000u)) {  // (no insert pass; a sharded round's own winner)
+                if ((!route && !(P.split & 2)) || (e & 0x10000u)) {  // (no insert pass; a sharded round's own winner)
                     seen_insert(P.seen, P.fp[(uint64_t)sHo[j] + r]);
                     own_ins++;
                 }
@@ -3709,7 +3738,7 @@ __global__ __launch_bounds__(XB_THREADS) void k_commit_items(KParams P) {
                 }
                 if (tot_ids & 1u) P.next[ring_wrap(oid + (tot_ids >> 1), P.rcap)] = word;
                 const uint32_t key = sb.z & 0xFFFFu;
-                if (P.route) {
+                if (route) {
                     // sharded round: the trace entry travels with the record to the state's next-level owner
                     const uint64_t pref = P.gid_parent_base + p;
                     P.xside[out] = make_uint4((uint32_t)pref, (uint32_t)(pref >> 32), key, size);
@@ -3736,7 +3765,7 @@ __global__ __launch_bounds__(XB_THREADS) void k_commit_items(KParams P) {
         }
     }
     if constexpr (!FUSE) {
-        if (P.route) block_count_add(own_ins, &P.sum[SUM_INS_COMMIT]);
+        if (route) block_count_add(own_ins, &P.sum[SUM_INS_COMMIT]);
     }
     if constexpr (FUSE) {
         // the last block to arrive finishes the level (k_commit's protocol); every wave's atomics and
@@ -4271,6 +4300,23 @@ static inline unsigned grid_for(uint64_t n) {
     return (unsigned)(n < cap ? (n ? n : 1) : cap);
 }
 
+// Blocks of `threads` threads of a kernel that a CU keeps resident: the runtime's answer, cut to what the
+// hardware admits -- at most 8 waves per SIMD, and at most 800 / (SGPRs rounded up to 16, + 16) of them; the
+// runtime's answer is one block too many in some SGPR ranges (82-96: it says 8, the CU takes 7).  The runtime
+// does not tell a kernel's SGPR count, so the most a gfx950 wave can hold (106: 6 waves) stands in for it: the
+// cut never over-states the residency, and binds only above 6 waves per SIMD.
+template <class K>
+static hipError_t resident_blocks(K kernel, int threads, int *blocks) {
+    int api = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&api, kernel, threads, 0);
+    if (e != hipSuccess) return e;
+    constexpr int SGPR_MAX = 106;
+    const int waves = std::min(8, 800 / ((SGPR_MAX + 15) / 16 * 16 + 16));  // per SIMD
+    const int per_simd = (threads + 255) / 256;                              // a block's waves on each of the 4 SIMDs
+    *blocks = std::max(1, std::min(api, waves / per_simd));
+    return hipSuccess;
+}
+
 template <int N, int V, int MR, bool BFV = false>
 struct Launch {
     static constexpr int MX = Spec<N, V, MR>::MAXS + (BFV ? Spec<N, V, MR>::MCAP : 0);
@@ -4289,10 +4335,26 @@ struct Launch {
         hipLaunchKernelGGL((k_expand<N, V, MR, M_FUSED, BFV>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64),
                            bm_bytes(P), s, P);
     }
-    static void split(const KParams &P, hipStream_t s) {
+    // (grid: the blocks at most -- whole resident generations, which the engine sizes from items_blocks; 0: a
+    // sharded round's fixed 2048.  The kernel's blocks stride over the batches, so each takes
+    // ceil(batches / grid) of them or one fewer)
+    static void split(const KParams &P, unsigned grid, hipStream_t s) {
         const uint64_t nbat = (P.p_end - P.p_begin + XB_PARENTS - 1) / XB_PARENTS;
-        hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, false, XB_PARENTS>), dim3((unsigned)(nbat < 2048 ? (nbat ? nbat : 1) : 2048)),
+        hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, false, XB_PARENTS>), dim3(items_grid(nbat, grid)),
                            dim3(items_threads<N, V, MR, false>()), 0, s, P);
+    }
+    static unsigned items_grid(uint64_t nbat, unsigned grid) {
+        const uint64_t cap = grid ? grid : 2048u;
+        return (unsigned)(nbat < cap ? (nbat ? nbat : 1) : cap);
+    }
+    // blocks per CU of the split expansion and of the split items commit (0: k_commit_split commits)
+    static hipError_t items_blocks(int *expand, int *commit) {
+        *commit = 0;
+        hipError_t e = resident_blocks(k_expand_items<N, V, MR, BFV, false, XB_PARENTS>, items_threads<N, V, MR, false>(), expand);
+        if constexpr (MX <= XB_THREADS) {
+            if (e == hipSuccess) e = resident_blocks(k_commit_items<N, V, MR, MX, false, 64, false>, XB_THREADS, commit);
+        }
+        return e;
     }
     static void hash_probe(const KParams &P, uint64_t np, hipStream_t s) {
         // four waves per block, a run of groups each: one group in a sharded round; else P.prun if set, or up to
@@ -4325,13 +4387,17 @@ struct Launch {
         }
         hipLaunchKernelGGL((k_commit<N, V, MR, BFV>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64), 0, s, P);
     }
-    static void commit_split(const KParams &P, uint64_t np, hipStream_t s) {
+    static void commit_split(const KParams &P, uint64_t np, unsigned grid, hipStream_t s) {
         const uint64_t blocks = (np + 255) / 256;  // a wave per 64 parents with winners (at most np of them)
         if constexpr (MX <= XB_THREADS) {
-            {  // a block per 64 parents with winners, records in LDS
+            {  // a block per 64 parents with winners, records in LDS (grid: as split's)
                 const uint64_t nbat = (np + 63) / 64;
-                hipLaunchKernelGGL((k_commit_items<N, V, MR, MX, false, 64>), dim3((unsigned)(nbat < 2048 ? (nbat ? nbat : 1) : 2048)),
-                                   dim3(XB_THREADS), 0, s, P);
+                if (P.route)
+                    hipLaunchKernelGGL((k_commit_items<N, V, MR, MX, false, 64, true>), dim3(items_grid(nbat, grid)),
+                                       dim3(XB_THREADS), 0, s, P);
+                else
+                    hipLaunchKernelGGL((k_commit_items<N, V, MR, MX, false, 64, false>), dim3(items_grid(nbat, grid)),
+                                       dim3(XB_THREADS), 0, s, P);
                 hipLaunchKernelGGL((k_commit_finish<MX, Spec<N, V, MR>::RECW_MAX>), dim3(1), dim3(64), 0, s, P);
                 return;
             }
@@ -4387,6 +4453,7 @@ static void fill(KernelSet *ks) {
     ks->single = &Launch<N, V, MR, BFV>::single;
     ks->fused = &Launch<N, V, MR, BFV>::fused;
     ks->split = &Launch<N, V, MR, BFV>::split;
+    ks->items_blocks = &Launch<N, V, MR, BFV>::items_blocks;
     ks->hash_probe = &Launch<N, V, MR, BFV>::hash_probe;
     ks->ctxw = ctx_words<N, V>();
     ks->insert = &Launch<N, V, MR, BFV>::insert;

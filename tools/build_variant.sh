@@ -12,8 +12,11 @@ case "$part" in
   # the sources as they are, beside the default build (an A/B of a source change: tools/ab_bench.sh)
   plain) ;;
   w1) FLAGS="$FLAGS -DRMC_WIDE_WAVES=1" ;;
-  # the item-parallel split expansion: waves / SIMD its registers are cut for (e.g. iw6)
+  # the item-parallel split expansion: waves / SIMD its registers are cut for, every instantiation (e.g. iw5;
+  # iw0: the compiler's choice; without it the kernel's own per-instantiation table, items_waves)
   iw*) FLAGS="$FLAGS -DRMC_ITEMS_WAVES=${part#iw}" ;;
+  # ... and the split chunks' items commit (e.g. cw5, cw0; commit_items_waves)
+  cw*) FLAGS="$FLAGS -DRMC_COMMIT_ITEMS_WAVES=${part#cw}" ;;
   # the probe pass (k_hash_probe): waves / SIMD its registers are cut for (e.g. pw6)
   pw*) FLAGS="$FLAGS -DRMC_PROBE_WAVES=${part#pw}" ;;
   # ... its threads per block for n <= 3 (e.g. nt128; with pb32 the same items per thread)
@@ -29,7 +32,7 @@ case "$part" in
   # n = 3 occupancy: expansion waves / SIMD, commit waves / SIMD, grid blocks / CU (e.g. n3w6c4g32)
   n3w*) X=${part#n3w}; W=${X%%c*}; X=${X#*c}; C=${X%%g*}; G=${X#*g}
         FLAGS="$FLAGS -DRMC_N3_WAVES=$W -DRMC_N3_COMMIT_WAVES=$C -DRMC_GRID_PER_CU=$G" ;;
-  *) echo "usage: $0 prof|plain|w1|iw<W>|pw<W>|nt<T>|pb<P>|fpb<P>|fcpb<P>|fw<W>|n3w<W>c<C>g<G>[+...]" >&2; exit 2 ;;
+  *) echo "usage: $0 prof|plain|w1|iw<W>|cw<W>|pw<W>|nt<T>|pb<P>|fpb<P>|fcpb<P>|fw<W>|n3w<W>c<C>g<G>[+...]" >&2; exit 2 ;;
 esac
 done
 OUT=${VARIANT_DIR:-build_$1}  # (VARIANT_DIR: another directory for the same flags)
