@@ -421,6 +421,75 @@ typedef struct rmc_graph_sink {
 } rmc_graph_sink;
 int rmc_set_graph(void *ctx, const rmc_graph_sink *sink);
 
+/* ---- reachability queries over the state graph (AG EF P; nothing in TLC) ---------------------------------
+ * Every mode above answers whether a state is reachable.  These answer, for each reachable state, whether a
+ * state with a property can still be reached FROM it -- e.g. "can a commit still happen from here" -- and
+ * name the first state from which it cannot.  rmc_set_graph_keep turns the graph pass on (with or without a
+ * sink: without one the pass runs and delivers nothing) and keeps what it resolves on the device: every
+ * edge's (src, dst) as u32 pairs in a store that grows by doubling, and per state a u16 with ALL seven
+ * compiled invariants evaluated on it, whatever the cfg lists and without check_invs' stop at the first
+ * FALSE one: bit b set = the invariant with bit index b is TRUE, bit 8 + b set = it raised the evaluation
+ * error (then bit b is clear).  A failed growth, 2^32 states or 2^32 edges fail that step with
+ * RMC_E_MEMORY.  When the run stops at an error the store holds exactly what graph mode delivers: the states
+ * with global id below the reported `distinct` and the edges up to TLC's stopping point, every dst < distinct.
+ * It has graph mode's limits (single GPU: RMC_E_ARG otherwise; no compact seen set; no rmc_resume) and
+ * composes with sinks, coverage and continuation as graph mode does.  rmc_set_graph_keep: after rmc_create
+ * or rmc_reset and before rmc_init (RMC_E_STATE otherwise); rmc_reset empties the store and keeps the
+ * setting.  Off by default, and then nothing is allocated or launched.
+ *
+ * What the verdict is about: the graph is the one TLC explores and dumps.  Each state is the first-found
+ * member of its SYMMETRY/VIEW class; the VIEW hides electionCount / restartCount, so a class's successors are
+ * those of its first-found member.  "Cannot" therefore includes states that are stuck only because
+ * MaxElection / MaxRestart are spent in that member.
+ *
+ * The analyses run on the device over a reverse CSR (in-degree histogram, exclusive scan, scatter through
+ * per-row cursors) that is built on first use and dropped when the graph grows; no reported number depends
+ * on the order inside a row.  They may be called between steps (the graph of the levels finished so far) or
+ * after the run; each returns RMC_E_STATE while keep is off or nothing has been kept or imported.
+ *   rmc_graph_reach         the target set is the states on which invariant `invariant_bit` (bit index 0..6)
+ *                           evaluated to `value` (1 TRUE, 0 FALSE); a state whose evaluation raised the error is
+ *                           in neither set.  A level-synchronous backward BFS from it, self-edges ignored:
+ *                           dist_out[g] (`states` entries, or NULL) = the fewest edges from g to a target, 0 for
+ *                           a target, 0xFFFFFFFF if there is no path.
+ *   rmc_graph_reach_levels  the last query's can / cannot counts per BFS level of the run ([0] = Init's level;
+ *                           an imported graph is one level); *n levels, RMC_E_ARG if cap is smaller.  The rows
+ *                           sum to can_reach / cannot_reach.
+ *   rmc_graph_shape         counts and degrees; cyclic_states by Kahn peeling: the states left after repeatedly
+ *                           removing every state with no non-self edge into a state still present.  0 = the
+ *                           graph has no cycle other than self-edges.
+ *   rmc_graph_inv_values    the u16 per state, cap >= states entries. */
+typedef struct rmc_reach_query {
+    uint32_t invariant_bit;   /* 0..6 */
+    int32_t value;            /* 1 = TRUE, 0 = FALSE */
+} rmc_reach_query;
+typedef struct rmc_reach_result {
+    uint64_t states, edges, self_edges;
+    uint64_t targets;         /* states in the target set */
+    uint64_t can_reach;       /* targets included (distance 0) */
+    uint64_t cannot_reach;
+    uint64_t first_cannot;    /* smallest global id that cannot reach a target; all ones if there is none */
+    int32_t first_cannot_level; /* its BFS level (1 = Init's level); 0 if there is none */
+    int32_t max_distance;     /* the farthest state that can */
+    int32_t init_distance;    /* -1: Init cannot */
+    uint32_t rounds;          /* frontier launches of the backward pass */
+    double seconds;           /* the backward pass */
+    double csr_seconds;       /* the build of the reverse CSR this query ran on (done once per kept graph) */
+} rmc_reach_result;
+/* (a struct tag only: the function below has the name) */
+struct rmc_graph_shape {
+    uint64_t states, edges, self_edges;
+    uint64_t back_edges;      /* dst < src */
+    uint64_t sinks;           /* states with no edge out at all */
+    uint64_t max_in, max_out; /* every edge counts, duplicates and self-edges included */
+    uint64_t cyclic_states;
+    uint64_t in_hist[64], out_hist[64]; /* states by degree; the last bin: 63 or more */
+};
+int rmc_set_graph_keep(void *ctx, int on);
+int rmc_graph_reach(void *ctx, const rmc_reach_query *q, rmc_reach_result *res, uint32_t *dist_out);
+int rmc_graph_reach_levels(void *ctx, uint64_t *can, uint64_t *cannot, uint32_t cap, uint32_t *n);
+int rmc_graph_shape(void *ctx, struct rmc_graph_shape *out);
+int rmc_graph_inv_values(void *ctx, uint16_t *out, uint64_t cap);
+
 /* Measurement support (bench.py): the random-probe peak of the seen-set layout -- `probes`
  * one-slot reads of 16-B slots at uniformly random indices of a 2^table_log2-slot table,
  * best of 3 timed launches; no model-checking state is touched. */
@@ -455,6 +524,13 @@ int rmc_fingerprints(void *ctx, const int32_t *unpacked, size_t stride_ints, uin
 int rmc_seen_contains(void *ctx, const uint64_t *fps, uint64_t n, uint8_t *out);
 /* 1 = TRUE, 0 = FALSE, RMC_EVAL_ERROR; one invariant bit */
 int rmc_eval_invariant(void *ctx, const int32_t *unpacked, uint32_t invariant_bit, int32_t *value);
+/* A graph from host arrays in place of a run's kept graph, so that tests reach the analyses' kernels with
+ * shapes no Raft graph has (cycles, hubs, long chains): n_states global ids, n_edges (src[i], dst[i]) pairs
+ * of them (RMC_E_ARG if one is past n_states), inv_values[g] in rmc_graph_inv_values' format.  Keep must be
+ * on and the context not mid-run (before rmc_init, or after the run has finished: RMC_E_STATE otherwise).
+ * It is one level as far as rmc_graph_reach_levels is concerned; the next rmc_init or rmc_reset drops it. */
+int rmc_graph_import(void *ctx, uint64_t n_states, uint64_t n_edges, const uint32_t *src, const uint32_t *dst,
+                     const uint16_t *inv_values);
 
 /* Unpacked state (int32), the interchange format of every hook:
  *   votedFor[n] (-1 = None)  currentTerm[n]  role[n] (0 F, 1 C, 2 L)  commitIndex[n]  logLen[n]

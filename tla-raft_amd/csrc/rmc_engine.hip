@@ -39,6 +39,7 @@
 #include "rmc.h"
 #include "rmc_kernels.h"
 #include "rmc_plan.h"
+#include "rmc_graph.h"
 #include "rmc_spec.h"
 
 #ifdef RMC_WITH_RCCL
@@ -714,7 +715,21 @@ struct rmc_ctx {
     // (k_edges: count pass, exclusive scan, write pass), each chunk's edges copied to pinned memory and
     // handed to the sink.  Single GPU, one level per host round trip (batch_ok), no compact seen set: the
     // ring at its budget reuses the expanded chunks' words, so migrate_compact fails the step instead.
-    bool graph = false;
+    // rmc_set_graph_keep: the pass runs with or without a sink (graph = gsink_on || gkeep) and what it resolves
+    // stays on the device in `kept` (rmc_graph.h): every chunk's (src, dst) after its write pass, every new
+    // record's invariant values (k_inv_values) after its k_gid_insert.  Off: nothing of it is allocated or launched.
+    bool graph = false, gsink_on = false, gkeep = false;
+    KeptGraph kept;
+    bool kept_imported = false;  // kept holds rmc_graph_import's graph, not a run's
+    template <class F>
+    void kept_call(F f) {
+        try {
+            kept.stream = stream;
+            f();
+        } catch (const GraphFail &g) {
+            throw Fail(g.code, g.msg);
+        }
+    }
     rmc_graph_sink gsink{};
     GSlot *gmap = nullptr;
     uint64_t gmap_cap = 0, gmap_count = 0;
@@ -803,6 +818,12 @@ struct rmc_ctx {
         Q.rcap = s.rcap;
         ks.gid_insert(Q, n, gid_map(), gid0, stream);
         gmap_count += n;
+        if (gkeep) {  // all seven invariants on the same records, by gid
+            kept_call([&] { kept.reserve_states(gid0 + n); });
+            ks.inv_values(Q, n, kept.inv + gid0, stream);
+            kept.set_states(gid0 + n);
+            kept.level_start.push_back(gid0);  // (one call per level, Init's included)
+        }
         if (!gsink.states) return;
         const size_t stride = RMC_UNPACKED_INTS(N, V, ks.MCAP);
         constexpr uint64_t PIECE = 4096;
@@ -853,14 +874,17 @@ struct rmc_ctx {
             E.off = g_off;
             HIPCHK(hipMemsetAsync(g_flag, 0, 4, stream));
             ks.edges(Q, E, stream);
-            HIPCHK(hipMemcpyAsync(hg_src, g_src, total * 8, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(hg_key, g_key, total * 4, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(hg_dst, g_dst, total * 8, hipMemcpyDeviceToHost, stream));
+            if (gsink.edges) {  // (nobody to deliver to: the edges stay on the device)
+                HIPCHK(hipMemcpyAsync(hg_src, g_src, total * 8, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(hg_key, g_key, total * 4, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(hg_dst, g_dst, total * 8, hipMemcpyDeviceToHost, stream));
+            }
             HIPCHK(hipMemcpyAsync(hg_word + 1, g_flag, 4, hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
             HIPCHK(hipGetLastError());
             if (hg_word[1] & 1u) throw Fail(RMC_E_STATE, "graph: edge to an unknown state (a successor's fingerprint is not in the gid map)");
             if (hg_word[1]) throw Fail(RMC_E_STATE, "graph: internal: a parent's successors do not fit the edge pass");
+            if (gkeep) kept_call([&] { kept.append_edges(g_src, g_dst, total); });  // (every dst resolved: checked above)
             if (gsink.edges && gsink.edges(gsink.user, total, (const uint64_t *)hg_src, hg_key, (const uint64_t *)hg_dst))
                 throw Fail(RMC_E_SINK, "the graph sink's edges callback failed");
         }
@@ -1567,6 +1591,7 @@ struct rmc_ctx {
         dfree(d_one); dfree(d_init_rec); dfree(d_init_fp); dfree(d_out); dfree(d_keys); dfree(d_cnt1); dfree(d_fp1); dfree(d_inv); dfree(d_err1); dfree(viol_loop);
         dfree(d_flags1); dfree(d_red);
         graph_free();
+        kept.free_all();
         dfree(d_sim_init); dfree(d_sim_len); dfree(d_sim_gen); dfree(d_sim_end); dfree(d_sim_keys); dfree(d_sim_err);
         sim_walks_cap = sim_keys_cap = 0;
         if (h_red) (void)hipHostFree(h_red);
@@ -2154,6 +2179,10 @@ struct rmc_ctx {
             s.T_count = 1;
         } else {
             init_full(rec, rw, iv);
+        }
+        if (gkeep) {  // (an imported graph gives way to the run's)
+            kept.clear();
+            kept_imported = false;
         }
         if (graph) {  // Init into the gid map and to the sink
             graph_alloc();
@@ -4387,6 +4416,8 @@ struct rmc_ctx {
             HIPCHK(hipMemsetAsync(gmap, 0, gmap_cap * sizeof(GSlot), stream));
             gmap_count = 0;
         }
+        kept.clear();  // (the setting stays, the buffers too)
+        kept_imported = false;
         violated = -1;
         err_ref = 0;
         err_last_slot = KEY_NONE;
@@ -4570,7 +4601,8 @@ int rmc_set_graph(void *ctx, const rmc_graph_sink *sink) {
         if (sink && sink->map_log2 > 40) throw Fail(RMC_E_ARG, "rmc_set_graph: map_log2 above 40");
         if (!sink) {  // off: nothing more is launched; what graph mode allocated stays with the context for a later
                       // rmc_set_graph of the same sizes (rmc_destroy frees it)
-            c->graph = false;
+            c->gsink_on = false;
+            c->graph = c->gkeep;
             c->gsink.user = nullptr;
             c->gsink.states = nullptr;
             c->gsink.edges = nullptr;
@@ -4584,8 +4616,79 @@ int rmc_set_graph(void *ctx, const rmc_graph_sink *sink) {
             HIPCHK(hipMemsetAsync(c->gmap, 0, c->gmap_cap * sizeof(GSlot), c->stream));
             c->gmap_count = 0;
         }
-        c->graph = true;
+        c->graph = c->gsink_on = true;
         c->gsink = *sink;
+        return RMC_OK;
+    });
+}
+
+int rmc_set_graph_keep(void *ctx, int on) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        if (c->inited) throw Fail(RMC_E_STATE, "rmc_set_graph_keep: after rmc_create or rmc_reset, before rmc_init");
+        if (on && (c->multi || c->W > 1 || c->cfg.world_size > 1 || c->cfg.virtual_shards > 1))
+            throw Fail(RMC_E_ARG, "rmc_set_graph_keep: single GPU only (world_size and virtual_shards at most 1)");
+        c->gkeep = on != 0;
+        c->graph = c->gsink_on || c->gkeep;
+        if (!c->gkeep) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            c->kept.free_all();
+            c->kept_imported = false;
+        }
+        return RMC_OK;
+    });
+}
+
+// the kept graph as it stands: the levels finished so far (or the imported graph)
+static void kept_ready(rmc_ctx *c, const char *who) {
+    if (!c->gkeep) throw Fail(RMC_E_STATE, std::string(who) + ": keep is off (rmc_set_graph_keep)");
+    if (c->kept.empty()) throw Fail(RMC_E_STATE, std::string(who) + ": nothing has been kept or imported");
+}
+
+int rmc_graph_reach(void *ctx, const rmc_reach_query *q, rmc_reach_result *res, uint32_t *dist_out) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_reach");
+        c->kept_call([&] { c->kept.reach(q, res, dist_out); });
+        return RMC_OK;
+    });
+}
+
+int rmc_graph_reach_levels(void *ctx, uint64_t *can, uint64_t *cannot, uint32_t cap, uint32_t *n) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_reach_levels");
+        c->kept_call([&] { c->kept.reach_levels(can, cannot, cap, n); });
+        return RMC_OK;
+    });
+}
+
+int rmc_graph_shape(void *ctx, struct rmc_graph_shape *out) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_shape");
+        c->kept_call([&] { c->kept.shape(out); });
+        return RMC_OK;
+    });
+}
+
+int rmc_graph_inv_values(void *ctx, uint16_t *out, uint64_t cap) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_inv_values");
+        c->kept_call([&] { c->kept.inv_values(out, cap); });
+        return RMC_OK;
+    });
+}
+
+int rmc_graph_import(void *ctx, uint64_t n_states, uint64_t n_edges, const uint32_t *src, const uint32_t *dst,
+                     const uint16_t *inv_values) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        if (!c->gkeep) throw Fail(RMC_E_STATE, "rmc_graph_import: keep is off (rmc_set_graph_keep)");
+        if (c->inited && !c->finished) throw Fail(RMC_E_STATE, "rmc_graph_import: the context is mid-run");
+        c->kept_call([&] { c->kept.import(n_states, n_edges, src, dst, inv_values); });
+        c->kept_imported = true;
         return RMC_OK;
     });
 }

@@ -332,6 +332,7 @@ struct KernelSet {
     void (*viol_scan)(const KParams &, uint64_t n, const ViolParams &, hipStream_t);  // continuation: violations among n records
     void (*fp_states)(const KParams &, uint64_t n, hipStream_t);  // fp of front[0..n) -> fp
     void (*inv_states)(const KParams &, uint64_t n, int32_t *out, hipStream_t); // per state: 1/0/-1 for inv_mask bits
+    void (*inv_values)(const KParams &, uint64_t n, uint16_t *out, hipStream_t);  // kept graph: all 7 invariants per record
     // host codec of the packed core (rmc_spec.h Codec)
     void (*encode)(const uint32_t *nibble_core, uint32_t *packed);
     void (*decode)(const uint32_t *packed, uint32_t *nibble_core);

@@ -2815,6 +2815,30 @@ __global__ __launch_bounds__(64) void k_inv_states(KParams P, uint64_t n, int32_
     for (int b = 0; b < 7; b++) out[i * 7 + b] = inv_eval<N, V>(c, b, mv);
 }
 
+// Kept graph (rmc_set_graph_keep): all seven invariants on n committed records (P.front / P.foff / P.fbase /
+// P.rcap name them, as for k_viol_scan), a lane per record, whatever the cfg lists and without check_invs'
+// stop at the first FALSE one.  out[i]: bit b = invariant b is TRUE, bit 8 + b = it raised the evaluation error.
+template <int N, int V, int MR>
+__global__ __launch_bounds__(256) void k_inv_values(KParams P, uint64_t n, uint16_t *out) {
+    using S = Spec<N, V, MR>;
+    using Lo = Layout<N, V>;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t start = rec_start<S::RECW_MAX>(P, i);
+        uint32_t packed[S::CCW], c[Lo::NW];
+#pragma unroll
+        for (int k = 0; k < S::CCW; k++) packed[k] = ring_word(P.front, start, (uint32_t)k, P.rcap);
+        decode_core<N, V>(packed, c);
+        const MsgView mv{P.front, ring_wrap(start + S::CCW, P.rcap), P.rcap, (c[Lo::W_MISC] >> 16) & 0xFFu, 0u, 0u, 0u,
+                         P.t.info};
+        uint32_t v = 0;
+        for (int b = 0; b < 7; b++) {
+            const int r = inv_eval<N, V>(c, b, mv);
+            v |= r == 1 ? 1u << b : r < 0 ? 1u << (8 + b) : 0u;
+        }
+        out[i] = (uint16_t)v;
+    }
+}
+
 // ---- fused level: winner counts, commit --------------------------------------------------------
 // Exclusive scan of one value per thread over a 1024-thread block (16 waves); *total gets the
 // block's sum.  ws holds 16 words of LDS.
@@ -4441,6 +4465,10 @@ struct Launch {
     static void invs(const KParams &P, uint64_t n, int32_t *out, hipStream_t s) {
         hipLaunchKernelGGL((k_inv_states<N, V, MR>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, P, n, out);
     }
+    static void inv_values(const KParams &P, uint64_t n, uint16_t *out, hipStream_t s) {
+        const uint64_t b = (n + 255) / 256;
+        if (n) hipLaunchKernelGGL((k_inv_values<N, V, MR>), dim3((unsigned)(b < 4096 ? b : 4096)), dim3(256), 0, s, P, n, out);
+    }
     static void enc(const uint32_t *c, uint32_t *o) { encode_core<N, V>(c, o); }
     static void dec(const uint32_t *w, uint32_t *c) { decode_core<N, V>(w, c); }
 };
@@ -4469,6 +4497,7 @@ static void fill(KernelSet *ks) {
     ks->edges = &Launch<N, V, MR, BFV>::edges;
     ks->fp_states = &Launch<N, V, MR>::fps;
     ks->inv_states = &Launch<N, V, MR>::invs;
+    ks->inv_values = &Launch<N, V, MR>::inv_values;
     ks->encode = &Launch<N, V, MR>::enc;
     ks->decode = &Launch<N, V, MR>::dec;
 }

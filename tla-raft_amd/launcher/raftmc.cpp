@@ -4,6 +4,7 @@
 //   raftmc -coverage MIN ... Raft.tla   (TLC's -coverage: the per-action distinct:generated report at the end)
 //   raftmc -continue ... Raft.tla       (TLC's -continue: search past invariant violations, count them per invariant)
 //   raftmc -dump FILE | -dump dot[,actionlabels] FILE ... Raft.tla   (TLC's -dump: the state graph, FILE.dump / FILE.dot)
+//   raftmc -canreach NAME[=FALSE] ... Raft.tla   (GPU-specific: which states can still reach one where NAME holds)
 //   raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config Raft.cfg] [-device D] [-msgcap C] Raft.tla
 //
 // Accepts the flags myrun.sh passes to TLC (myrun.sh:3), reads the same Raft.tla /
@@ -303,7 +304,7 @@ struct DumpSink {
 int usage(const char *msg) {
     std::fprintf(stderr, "raftmc: %s\nusage: raftmc [-deadlock] [-workers N] [-config FILE.cfg] [-device D] "
                          "[-gpus N [-onerank] [-shardmin K]] [-msgcap C] [-seenlog2 K] [-checkpoint MIN] [-metadir DIR] "
-                         "[-recover DIR] [-coverage MIN] [-continue] [-dump [dot[,actionlabels]] FILE] FILE.tla\n"
+                         "[-recover DIR] [-coverage MIN] [-continue] [-dump [dot[,actionlabels]] FILE] [-canreach NAME[=FALSE]]... FILE.tla\n"
                          "       raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config FILE.cfg] [-device D] "
                          "[-msgcap C] FILE.tla\n"
                          "  -coverage MIN  per-action coverage (distinct:generated) at the end of the search; the interval "
@@ -313,6 +314,10 @@ int usage(const char *msg) {
                          "  -dump FILE  every distinct state in discovery order to FILE.dump; -dump dot FILE: the state graph "
                          "(states and every edge) to FILE.dot, with dot,actionlabels the edges carry their action's name; "
                          "one GPU, not with -simulate or -recover\n"
+                         "  -canreach NAME[=FALSE]  (GPU-specific, repeatable) after the search: how many distinct states can "
+                         "still reach a state on which invariant NAME is TRUE (=FALSE: is FALSE), and the behaviour to the first "
+                         "that cannot; NAME is one of Inv NoSplitVote RaftCanCommt FollowerCanCommit CommitAll NoAllCommit "
+                         "ExistLeaderAndCandidate, in the cfg or not; one GPU, not with -simulate or -recover\n"
                          "  -simulate  random behaviours instead of the breadth-first search; num=N of them (default "
                          "1000000; TLC's default is unbounded)\n"
                          "  -depth D   states per behaviour at most (default 100, as TLC)\n"
@@ -514,6 +519,8 @@ int main(int argc, char **argv) {
     bool cont = false;                                   // TLC -continue
     bool dump = false, dump_dot = false, dump_labels = false;  // TLC -dump [dot[,options]] FILE
     std::string dump_file, dump_bad;
+    std::vector<std::pair<int, int>> canreach;  // -canreach NAME[=FALSE]: (invariant bit, value)
+    std::string canreach_bad;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *f) -> const char * {
@@ -559,6 +566,23 @@ int main(int argc, char **argv) {
             }
             dump_file = v;
         }
+        else if (a == "-canreach") {
+            std::string v = need("-canreach");
+            int value = 1;
+            const size_t eq = v.find('=');
+            std::string name = v.substr(0, eq);
+            if (eq != std::string::npos) {
+                const std::string t = v.substr(eq + 1);
+                if (t == "FALSE") value = 0;
+                else if (t != "TRUE") canreach_bad = v;
+            }
+            int bit = -1;
+            if (name == "LeaderHasAllCommittedEntries") bit = 0;
+            for (int b = 0; b < 7 && bit < 0; b++)
+                if (name == kInvNames[b]) bit = b;
+            if (bit < 0 && canreach_bad.empty()) canreach_bad = v;
+            canreach.push_back({bit, value});
+        }
         else if (a == "-depth") sim_depth = std::atoll(need("-depth"));
         else if (a == "-seed") { sim_seed = (unsigned long long)std::strtoll(need("-seed"), nullptr, 10); seed_given = true; }
         else if (a == "-metadir") metadir = need("-metadir");
@@ -587,6 +611,14 @@ int main(int argc, char **argv) {
         const std::string ext = dump_dot ? ".dot" : ".dump";  // (TLC appends the extension unless it is there)
         if (dump_file.size() < ext.size() || dump_file.compare(dump_file.size() - ext.size(), ext.size(), ext) != 0)
             dump_file += ext;
+    }
+    if (!canreach.empty()) {  // refused before anything touches a device
+        if (!canreach_bad.empty())
+            return usage(("-canreach " + canreach_bad + ": NAME[=TRUE|=FALSE] with NAME one of Inv, NoSplitVote, RaftCanCommt, "
+                          "FollowerCanCommit, CommitAll, NoAllCommit, ExistLeaderAndCandidate").c_str());
+        if (simulate) return usage("-canreach cannot be combined with -simulate");
+        if (!recover_dir.empty()) return usage("-canreach cannot be combined with -recover (checkpoints do not carry the state graph)");
+        if (gpus > 1 || onerank) return usage("-canreach runs on one GPU (no -gpus)");
     }
     if (simulate) {  // refused before anything touches a device
         if (sim_bad) return usage("-simulate takes num=N with N >= 1");
@@ -667,23 +699,7 @@ int main(int argc, char **argv) {
         }
         return out;
     };
-    auto print_error = [&](const std::vector<Step> &steps, const rmc_config &cfg, int status, int violated) -> int {
-        int exit_code = 0;
-        if (status == RMC_VIOLATION) {
-            std::printf("Error: Invariant %s is violated.\n", inv_name(violated).c_str());
-            exit_code = 12;
-        } else if (status == RMC_ASSERT) {
-            std::printf("Error: The first argument of Assert evaluated to FALSE; the second argument was:\n\"split brain\"\n");
-            exit_code = 14;
-        } else if (status == RMC_EVAL_ERROR) {
-            std::printf("Error: Evaluating invariant %s failed.\nAttempted to apply a tuple to an index out of its domain "
-                        "(logs[p][index], %s.tla line 499).\n", kInvNames[violated], pm.module.c_str());
-            exit_code = 75;
-        } else if (status == RMC_DEADLOCK) {
-            std::printf("Error: Deadlock reached.\n");
-            exit_code = 11;
-        }
-        std::printf("Error: The behavior up to this point is:\n");
+    auto print_behavior = [&](const std::vector<Step> &steps, const rmc_config &cfg) {
         std::vector<std::string> names(kActionNames, kActionNames + 13);
         names.insert(names.end(), kBfNames, kBfNames + 3);  // 13..15
         std::vector<Loc> locs = action_locations(tla, names);
@@ -705,6 +721,65 @@ int main(int argc, char **argv) {
             for (int q = 0; q < cfg.n_servers; q++) prev_role[q] = buf[2 * cfg.n_servers + q];  // unpacked: vf, ct, role
             std::printf("%s\n", pr.state(buf.data()).c_str());
         }
+    };
+    // The behaviour from Init to the explored state `gid`: its slot keys (rmc_state_path) replayed from Init
+    // (Raft.tla:93-105) through rmc_successors; empty if a step does not resolve.
+    auto path_steps = [&](void *ctx, const rmc_config &cfg, uint64_t gid) {
+        std::vector<Step> out;
+        const int n = cfg.n_servers, V = cfg.n_vals;
+        uint32_t len = 0;
+        std::vector<uint32_t> keys(4096);
+        if (rmc_state_path(ctx, gid, keys.data(), nullptr, (uint32_t)keys.size(), &len) < 0) return out;
+        const size_t stride = RMC_UNPACKED_INTS(5, 3, 256);
+        Step st{std::vector<int32_t>(stride, 0), -1, 0, 0};
+        int32_t *u = st.buf.data();
+        for (int i = 0; i < n; i++) {
+            u[i] = -1;                              // votedFor = None
+            u[3 * n + i] = 1;                       // commitIndex
+            u[4 * n + i] = 1;                       // Len(logs[i]): the entry (0, None)
+            u[5 * n + i * (V + 1) * 2 + 1] = -1;
+        }
+        int32_t *m = u + 5 * n + n * (V + 1) * 2;
+        for (int i = 0; i < n * n; i++) {
+            m[i] = 1;          // matchIndex
+            m[n * n + i] = 2;  // nextIndex
+        }
+        for (int v = 0; v < V; v++) m[3 * n * n + 2 + v] = -1;  // valSent = None
+        out.push_back(st);
+        const uint32_t cap = 1024;
+        std::vector<int32_t> succ(cap * stride);
+        std::vector<uint32_t> sk(cap);
+        for (uint32_t i = 1; i < len; i++) {
+            uint32_t cnt = 0;
+            if (rmc_successors(ctx, out.back().buf.data(), succ.data(), stride, cap, sk.data(), nullptr, &cnt) != RMC_OK)
+                return std::vector<Step>();
+            uint32_t j = 0;
+            while (j < cnt && sk[j] != keys[i]) j++;
+            if (j == cnt) return std::vector<Step>();
+            Step nx{std::vector<int32_t>(succ.begin() + (size_t)j * stride, succ.begin() + (size_t)(j + 1) * stride),
+                    (int32_t)((keys[i] >> 16) & 0xFF), (int32_t)(keys[i] >> 24), (int32_t)(keys[i] & 0xFFFF)};
+            out.push_back(std::move(nx));
+        }
+        return out;
+    };
+    auto print_error = [&](const std::vector<Step> &steps, const rmc_config &cfg, int status, int violated) -> int {
+        int exit_code = 0;
+        if (status == RMC_VIOLATION) {
+            std::printf("Error: Invariant %s is violated.\n", inv_name(violated).c_str());
+            exit_code = 12;
+        } else if (status == RMC_ASSERT) {
+            std::printf("Error: The first argument of Assert evaluated to FALSE; the second argument was:\n\"split brain\"\n");
+            exit_code = 14;
+        } else if (status == RMC_EVAL_ERROR) {
+            std::printf("Error: Evaluating invariant %s failed.\nAttempted to apply a tuple to an index out of its domain "
+                        "(logs[p][index], %s.tla line 499).\n", kInvNames[violated], pm.module.c_str());
+            exit_code = 75;
+        } else if (status == RMC_DEADLOCK) {
+            std::printf("Error: Deadlock reached.\n");
+            exit_code = 11;
+        }
+        std::printf("Error: The behavior up to this point is:\n");
+        print_behavior(steps, cfg);
         return exit_code;
     };
     auto check = [&](const rmc_config &cfg) -> int {
@@ -732,6 +807,11 @@ int main(int argc, char **argv) {
         return 75;
     }
     if (cont && rmc_set_continue(ctx, 1) < 0) {
+        std::printf("Error: %s\n", rmc_last_error(ctx));
+        rmc_destroy(ctx);
+        return 75;
+    }
+    if (!canreach.empty() && rmc_set_graph_keep(ctx, 1) < 0) {
         std::printf("Error: %s\n", rmc_last_error(ctx));
         rmc_destroy(ctx);
         return 75;
@@ -809,7 +889,7 @@ int main(int argc, char **argv) {
         const auto now = std::chrono::steady_clock::now();
         // (-dump runs a level per call where the plain run's first call covers a device-driven batch of them: its
         // first report waits for the interval or the closing one, so both runs print the same lines)
-        if ((!reported && !dump) || std::chrono::duration<double>(now - last_progress).count() >= progress_s) {
+        if ((!reported && !dump && canreach.empty()) || std::chrono::duration<double>(now - last_progress).count() >= progress_s) {
             progress(last);
             reported = true;
             printed_level = last.level;
@@ -871,6 +951,36 @@ int main(int argc, char **argv) {
         if (!violations) std::printf("Model checking completed. No error has been found.\n");
     } else {
         exit_code = print_error(err_steps, cfg, res.status, res.violated);
+    }
+    // -canreach: one line per query over the graph of the search (what -dump writes), then the first state that cannot
+    for (const auto &cq : canreach) {
+        rmc_reach_query q{(uint32_t)cq.first, cq.second};
+        rmc_reach_result rr;
+        if (rmc_graph_reach(ctx, &q, &rr, nullptr) < 0) {
+            std::printf("Error: no reachability of %s: %s\n", kInvNames[cq.first], rmc_last_error(ctx));
+            continue;
+        }
+        const std::string init_d = rr.init_distance < 0 ? std::string("cannot") : std::to_string(rr.init_distance) + " steps";
+        std::printf("Reachability of %s = %s: %llu of %llu distinct states satisfy it, %llu can reach one (farthest: %d steps, "
+                    "Init: %s), %llu cannot", kInvNames[cq.first], cq.second ? "TRUE" : "FALSE", (unsigned long long)rr.targets,
+                    (unsigned long long)rr.states, (unsigned long long)rr.can_reach, rr.max_distance, init_d.c_str(),
+                    (unsigned long long)rr.cannot_reach);
+        if (rr.cannot_reach) std::printf(" (first at depth %d).\n", rr.first_cannot_level);
+        else std::printf(".\n");
+        if (rr.cannot_reach) {
+            const std::vector<Step> steps = path_steps(ctx, cfg, rr.first_cannot);
+            if (steps.empty()) std::printf("Error: no behaviour to state %llu: %s\n", (unsigned long long)rr.first_cannot, rmc_last_error(ctx));
+            else {
+                std::printf("The behavior up to the first state that cannot is:\n");
+                print_behavior(steps, cfg);
+            }
+        }
+    }
+    if (!canreach.empty()) {
+        struct rmc_graph_shape gsh;
+        if (rmc_graph_shape(ctx, &gsh) < 0) std::printf("Error: no graph shape: %s\n", rmc_last_error(ctx));
+        else if (!gsh.cyclic_states) std::printf("The state graph has no cycle other than self-loops.\n");
+        else std::printf("The state graph has %llu states on or leading to cycles.\n", (unsigned long long)gsh.cyclic_states);
     }
     rmc_coverage cov;
     const int cov_rc = coverage && cfg.rank == 0 ? rmc_get_coverage(ctx, &cov) : RMC_OK;

@@ -125,6 +125,25 @@ class _GraphSink(ctypes.Structure):
                 ("chunk_parents", ctypes.c_uint32), ("map_log2", ctypes.c_uint32)]
 
 
+class _ReachQuery(ctypes.Structure):
+    _fields_ = [("invariant_bit", ctypes.c_uint32), ("value", ctypes.c_int32)]
+
+
+class _ReachResult(ctypes.Structure):
+    _fields_ = [("states", ctypes.c_uint64), ("edges", ctypes.c_uint64), ("self_edges", ctypes.c_uint64),
+                ("targets", ctypes.c_uint64), ("can_reach", ctypes.c_uint64), ("cannot_reach", ctypes.c_uint64),
+                ("first_cannot", ctypes.c_uint64), ("first_cannot_level", ctypes.c_int32),
+                ("max_distance", ctypes.c_int32), ("init_distance", ctypes.c_int32), ("rounds", ctypes.c_uint32),
+                ("seconds", ctypes.c_double), ("csr_seconds", ctypes.c_double)]
+
+
+class _GraphShape(ctypes.Structure):
+    _fields_ = [("states", ctypes.c_uint64), ("edges", ctypes.c_uint64), ("self_edges", ctypes.c_uint64),
+                ("back_edges", ctypes.c_uint64), ("sinks", ctypes.c_uint64), ("max_in", ctypes.c_uint64),
+                ("max_out", ctypes.c_uint64), ("cyclic_states", ctypes.c_uint64),
+                ("in_hist", ctypes.c_uint64 * 64), ("out_hist", ctypes.c_uint64 * 64)]
+
+
 _lib = None
 
 
@@ -183,6 +202,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.rmc_violation_trace.argtypes = [vp, u32]
     if hasattr(lib, "rmc_set_graph"):  # (likewise)
         lib.rmc_set_graph.argtypes = [vp, P(_GraphSink)]
+    if hasattr(lib, "rmc_set_graph_keep"):  # (likewise)
+        lib.rmc_set_graph_keep.argtypes = [vp, i32]
+        lib.rmc_graph_reach.argtypes = [vp, P(_ReachQuery), P(_ReachResult), vp]
+        lib.rmc_graph_reach_levels.argtypes = [vp, P(u64), P(u64), u32, P(u32)]
+        lib.rmc_graph_shape.argtypes = [vp, P(_GraphShape)]
+        lib.rmc_graph_inv_values.argtypes = [vp, vp, u64]
+        lib.rmc_graph_import.argtypes = [vp, u64, u64, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -537,6 +563,28 @@ class Result:
 
 
 @dataclass
+class ReachResult:
+    """rmc_graph_reach's result (include/rmc.h rmc_reach_result); first_cannot / first_cannot_level / init_distance
+    are None where the library reports none; dist: numpy u32 per state (0xFFFFFFFF = cannot) with want_dist."""
+    invariant: str
+    value: bool
+    states: int
+    edges: int
+    self_edges: int
+    targets: int
+    can_reach: int
+    cannot_reach: int
+    first_cannot: Optional[int]
+    first_cannot_level: Optional[int]
+    max_distance: int
+    init_distance: Optional[int]
+    rounds: int
+    seconds: float
+    csr_seconds: float
+    dist: object = None
+
+
+@dataclass
 class SimResult:
     """ModelChecker.simulate: the accounted walks (0..err_walk on an error, all of them otherwise)."""
     status: str
@@ -605,6 +653,7 @@ class ModelChecker:
         st = _LevelStats()
         self._check(self.lib.rmc_init(self.h, ctypes.byref(st)))
         self._inited = True
+        self._g_import_n = None
         ls = self._stats(st)
         self._levels_list().append(ls)
         return ls
@@ -612,6 +661,7 @@ class ModelChecker:
     def reset(self) -> None:
         """Start over from Init on the next run(), keeping the device buffers."""
         self._check(self.lib.rmc_reset(self.h))
+        self._g_import_n = None
         self.levels = []
         self._inited = False
 
@@ -651,6 +701,8 @@ class ModelChecker:
         if getattr(self, "_runbuf", None) is None:
             self._runbuf = (_LevelStats * cap)()  # reused by every run of this checker
         n = ctypes.c_uint32()
+        if not getattr(self, "_inited", False):
+            self._g_import_n = None
         self._check(self.lib.rmc_run_levels(self.h, self._runbuf, cap, ctypes.byref(n), None))
         self._inited = True
         lazy = _LazyLevels(self._runbuf, n.value)
@@ -813,6 +865,72 @@ class ModelChecker:
         self._graph_check()
         n, V = self.cfg.n_servers, self.cfg.n_vals
         return [unpacked_to_state(row.tolist(), n, V) for part in self._g_states for row in part]
+
+    # ---- reachability queries over the kept state graph (include/rmc.h rmc_set_graph_keep) ----
+    def set_graph_keep(self, on: bool = True) -> None:
+        """Keep the run's state graph on the device for graph_reach() / graph_shape(): the graph pass runs
+        with or without set_graph().  On a fresh or reset checker, before init() / run()."""
+        if not hasattr(self.lib, "rmc_set_graph_keep"):
+            raise RmcError("this librmc.so keeps no graph (rmc_set_graph_keep): rebuild it")
+        self._check(self.lib.rmc_set_graph_keep(self.h, 1 if on else 0))
+
+    def graph_reach(self, invariant: str, value: bool = True, want_dist: bool = False) -> ReachResult:
+        """Which states can still reach a state on which `invariant` is `value`: a backward BFS on the device
+        over the kept graph (the levels finished so far, or the imported graph)."""
+        import numpy as np
+        q, r = _ReachQuery(self._inv_bit(invariant), 1 if value else 0), _ReachResult()
+        dist = None
+        if want_dist:
+            dist = np.empty(self._kept_states(), dtype=np.uint32)
+        self._check(self.lib.rmc_graph_reach(self.h, ctypes.byref(q), ctypes.byref(r),
+                                             dist.ctypes.data if dist is not None else None))
+        none = r.first_cannot == 0xFFFFFFFFFFFFFFFF
+        return ReachResult(invariant, bool(value), r.states, r.edges, r.self_edges, r.targets, r.can_reach,
+                           r.cannot_reach, None if none else r.first_cannot, None if none else r.first_cannot_level,
+                           r.max_distance, None if r.init_distance < 0 else r.init_distance, r.rounds, r.seconds,
+                           r.csr_seconds, dist)
+
+    def _kept_states(self) -> int:
+        # the kept graph's states: the imported graph's, else every state found so far (also at an error stop)
+        n = getattr(self, "_g_import_n", None)
+        return n if n is not None else self.result().distinct
+
+    def graph_reach_levels(self) -> List[Tuple[int, int]]:
+        """The last graph_reach()'s (can, cannot) per BFS level ([0]: Init's level)."""
+        cap = 4096
+        can, cannot, n = (ctypes.c_uint64 * cap)(), (ctypes.c_uint64 * cap)(), ctypes.c_uint32()
+        self._check(self.lib.rmc_graph_reach_levels(self.h, can, cannot, cap, ctypes.byref(n)))
+        return list(zip(can[:n.value], cannot[:n.value]))
+
+    def graph_shape(self) -> dict:
+        """Counts and degrees of the kept graph (include/rmc.h rmc_graph_shape) as a dict; in_hist / out_hist
+        are lists of 64 (the last bin: 63 or more)."""
+        g = _GraphShape()
+        self._check(self.lib.rmc_graph_shape(self.h, ctypes.byref(g)))
+        out = {k: getattr(g, k) for k in ("states", "edges", "self_edges", "back_edges", "sinks", "max_in", "max_out",
+                                           "cyclic_states")}
+        out["in_hist"], out["out_hist"] = list(g.in_hist), list(g.out_hist)
+        return out
+
+    def graph_inv_values(self):
+        """numpy u16 per state of the kept graph: bit b = invariant INVARIANT_BY_BIT[b] is TRUE, bit 8 + b = it
+        raised the evaluation error."""
+        import numpy as np
+        out = np.empty(self._kept_states(), dtype=np.uint16)
+        self._check(self.lib.rmc_graph_inv_values(self.h, out.ctypes.data, out.size))
+        return out
+
+    def graph_import(self, n_states: int, src, dst, inv_values) -> None:
+        """A graph from arrays in place of a run's kept graph (test hook; include/rmc.h rmc_graph_import)."""
+        import numpy as np
+        s = np.ascontiguousarray(src, dtype=np.uint32)
+        d = np.ascontiguousarray(dst, dtype=np.uint32)
+        v = np.ascontiguousarray(inv_values, dtype=np.uint16)
+        if s.shape != d.shape or s.ndim != 1 or v.shape != (n_states,):
+            raise RmcError("RMC_E_ARG: graph_import: src / dst of one length, inv_values of n_states entries")
+        self._check(self.lib.rmc_graph_import(self.h, n_states, s.size, s.ctypes.data if s.size else None,
+                                              d.ctypes.data if d.size else None, v.ctypes.data))
+        self._g_import_n = n_states
 
     def trace(self) -> List[Tuple[Optional[Tuple[int, int, int]], dict]]:
         n = ctypes.c_uint32()
