@@ -80,11 +80,18 @@ extern "C" {
  *     64 lanes  (msg_cap 1..64):   (2,1) (2,2) (3,1) (3,2) (3,3)
  *     128 lanes (msg_cap above 64): (3,1) (3,2) (4,1) (4,2) (5,1) (5,2)
  * each with and without RMC_SPEC_BECOME_FOLLOWER.  So 4 and 5 servers need the 128 lanes (the
- * default there) and take at most 2 values; 3 values exist only at 3 servers with 64 lanes. */
+ * default there) and take at most 2 values; 3 values exist only at 3 servers with 64 lanes.
+ *
+ * Message ids are 16 bit, so the static message universe of (n_servers, n_vals, max_election) must hold
+ * fewer than 65,535 records.  That caps max_election per pair:
+ *     (2,1) (2,2) (3,1) (4,1) (5,1): 7     (3,2): 6     (3,3): 4     (4,2): 5     (5,2): 4
+ * rmc_create refuses a larger one with RMC_E_ARG ("... max_election is at most 6 for this pair"), like a
+ * pair without kernels before it touches the device, and rmc_parse_config refuses such a cfg with
+ * RMC_E_PARSE and the same limit in its text. */
 typedef struct rmc_config {
     int32_t n_servers;      /* |Servers|   Raft.cfg:18, 2..5 (see the table above) */
     int32_t n_vals;         /* |Vals|      Raft.cfg:21, 1..2; 3 at 3 servers with 64 lanes */
-    int32_t max_election;   /* MaxElection Raft.cfg:4,  0..7 */
+    int32_t max_election;   /* MaxElection Raft.cfg:4,  0..7, and at most the pair's cap above */
     int32_t max_restart;    /* MaxRestart  Raft.cfg:3,  0..15 */
     uint32_t invariants;    /* RMC_INV_* bits (order: invariant_order) */
     int32_t check_deadlock; /* 0 = TLC -deadlock (myrun.sh:3) */
@@ -495,6 +502,8 @@ int rmc_graph_inv_values(void *ctx, uint16_t *out, uint64_t cap);
  * best of 3 timed launches; no model-checking state is touched. */
 int rmc_probe_peak(int device, uint32_t table_log2, uint64_t probes, double *probes_per_s, double *seconds);
 
+/* The text of the context's last error; ctx = NULL: that of the calling thread's last failed rmc_create
+ * (which leaves no context to ask). */
 const char *rmc_last_error(void *ctx);
 void rmc_destroy(void *ctx);
 /* Frees every device allocation of the context (seen set, frontier ring, chunk buffers, streams, the

@@ -65,14 +65,15 @@ def c_lib():
     return lib
 
 
-def c_successors(lib, cfg, d, cap_msgs=160):
+def c_successors(lib, cfg, d, cap_msgs=160, flags=0):
+    """orc_successors; flags are the C oracle's spec flags (2 = the BecomeFollower variant, tla:420)."""
     u = state_to_unpacked(d, cfg.n, cfg.V)
     inp = (ctypes.c_int32 * len(u))(*u)
     stride = unpacked_len(cfg.n, cfg.V, cap_msgs)
     cap = 1024
     out = (ctypes.c_int32 * (stride * cap))()
     keys = (ctypes.c_uint32 * cap)()
-    cnt = lib.orc_successors(cfg.n, cfg.V, cfg.max_election, cfg.max_restart, 0, inp, out, stride, cap, keys)
+    cnt = lib.orc_successors(cfg.n, cfg.V, cfg.max_election, cfg.max_restart, flags, inp, out, stride, cap, keys)
     if cnt < 0:
         return cnt, []
     res = []
@@ -98,16 +99,18 @@ def c_inv(lib, cfg, d, i):
     return None if r not in (0, 1) else bool(r)
 
 
-def walk(lib, cfg, rng, prefix, steps, w_elect, mcap):
+def walk(lib, cfg, rng, prefix, steps, w_elect, mcap, weight=None, flags=0):
     """Continue a path from Init: at every step one successor (C oracle, orc_successors) whose exact
     canonical class (orc_canon_hash) the path has not visited, drawn with weight 3 if it adds a
     message, 1 if not, `w_elect` for BecomeCandidate / Restart (elections and restarts are bounded,
-    tla:108,411: spending them late leaves room for more replication traffic per term)."""
+    tla:108,411: spending them late leaves room for more replication traffic per term).
+    `weight(st, key, t)`, if given, replaces those weights (make_golden_highterm.py spends the
+    elections instead); `flags` are the C oracle's spec flags."""
     path = list(prefix)
     seen = {c_canon(lib, cfg, d) for d in path}
     st = path[-1]
     for _ in range(steps):
-        cnt, succ = c_successors(lib, cfg, st)
+        cnt, succ = c_successors(lib, cfg, st, flags=flags)
         if cnt <= 0:
             break
         cand, wts = [], []
@@ -118,7 +121,10 @@ def walk(lib, cfg, rng, prefix, steps, w_elect, mcap):
             if h in seen:
                 continue
             cand.append((t, h))
-            wts.append(w_elect if a in (R.A_BC, R.A_RS) else (3.0 if len(t["msgs"]) > len(st["msgs"]) else 1.0))
+            if weight is not None:
+                wts.append(weight(st, (s, a, w), t))
+            else:
+                wts.append(w_elect if a in (R.A_BC, R.A_RS) else (3.0 if len(t["msgs"]) > len(st["msgs"]) else 1.0))
         if not cand:
             break
         st, h = rng.choices(cand, weights=wts)[0]
@@ -174,6 +180,59 @@ def augment(cfg, rng, st, total):
     return R.State(**{**st.__dict__, "msgs": frozenset(msgs)})
 
 
+def state_record(lib, cfg, name, rng, k, st, canon_ids, c_of_py, flags=0):
+    """The fixture record of one state (walk depth k; k < 0: synthetic): successors in TLC order by both
+    oracles, a server-permuted copy, the canonical class of every successor (ids shared through
+    canon_ids / c_of_py across the configuration) and the seven invariants on it and its first successors."""
+    n, V = cfg.n, cfg.V
+    d = R.state_to_json(st)
+    try:
+        succ = R.successors(cfg, st)
+    except R.AssertionFailure:  # UpdateTerm's Assert (tla:185): a leader with a same-term AppendReq
+        assert c_successors(lib, cfg, d, flags=flags)[0] == -1, (name, "C oracle misses the Assert")
+        return dict(depth=abs(k), synthetic=k < 0, nmsgs=len(st.msgs), state=d, assert_fails=True)
+    assert all(len(log) <= V + 1 for _, t in succ for log in t.logs), (name, "log past V + 1")
+    cnt, csucc = c_successors(lib, cfg, d, flags=flags)
+    assert cnt == len(succ), (name, cnt, len(succ))
+    for (kk, t), (ck, cd) in zip(succ, csucc):
+        assert list(kk) == ck and R.state_to_json(t) == cd, (name, kk, ck)
+    perm = list(range(n))
+    rng.shuffle(perm)
+    pv = R.permute_view(st.view(), perm)
+    inv = [0] * n
+    for a in range(n):
+        inv[perm[a]] = a
+    pst = R.State(votedFor=pv[0], currentTerm=pv[1], logs=pv[2], matchIndex=pv[3], nextIndex=pv[4],
+                  commitIndex=pv[5], msgs=frozenset(pv[6]), role=pv[7], electionCount=st.electionCount,
+                  restartCount=st.restartCount,
+                  pendingResponse=tuple(tuple(st.pendingResponse[inv[a]][inv[b]] for b in range(n))
+                                        for a in range(n)),
+                  valSent=st.valSent)
+    assert R.canonical(cfg, pst) == R.canonical(cfg, st)
+    sjs = []
+    for kk, t in succ:
+        tj = R.state_to_json(t)
+        c = R.canonical(cfg, t)
+        cid = canon_ids.setdefault(c, len(canon_ids))
+        ch = c_canon(lib, cfg, tj)
+        assert c_of_py.setdefault(ch, cid) == cid, (name, "C/Python canonical partitions differ")
+        sjs.append(dict(key=list(kk), state=tj, canon=cid))
+    invs = {}
+    for sc_st, sc_d, tag in [(st, d, "state")] + [(t, R.state_to_json(t), f"succ{j}")
+                                                 for j, (_, t) in enumerate(succ[:4])]:
+        vals = []
+        for ii, nm in enumerate(INV_NAMES):
+            try:
+                pyv = R.INV_FUNCS[nm](cfg, sc_st)
+            except R.EvalError:
+                pyv = None
+            assert c_inv(lib, cfg, sc_d, ii) == pyv, (name, nm, tag)
+            vals.append(pyv)
+        invs[tag] = vals
+    return dict(depth=abs(k), synthetic=k < 0, nmsgs=len(st.msgs), assert_fails=False, state=d, permuted=R.state_to_json(pst),
+                successors=sjs, invariants=invs)
+
+
 def one_config(spec):
     name, n, V, E, Rr, walks, n_synth, keep, mcap = spec
     cfg = R.Config(n=n, V=V, max_election=E, max_restart=Rr)
@@ -208,53 +267,7 @@ def one_config(spec):
         synth.append((k, augment(cfg, rng, st, rng.randint(mmax + 1, mcap))))
     items, canon_ids, c_of_py = [], {}, {}
     for k, st in [(k, st) for k, st in picked] + [(-k, st) for k, st in synth]:
-        d = R.state_to_json(st)
-        try:
-            succ = R.successors(cfg, st)
-        except R.AssertionFailure:  # UpdateTerm's Assert (tla:185): a leader with a same-term AppendReq
-            assert c_successors(lib, cfg, d)[0] == -1, (name, "C oracle misses the Assert")
-            items.append(dict(depth=abs(k), synthetic=k < 0, nmsgs=len(st.msgs), state=d, assert_fails=True))
-            continue
-        assert all(len(log) <= V + 1 for _, t in succ for log in t.logs), (name, "log past V + 1")
-        cnt, csucc = c_successors(lib, cfg, d)
-        assert cnt == len(succ), (name, cnt, len(succ))
-        for (kk, t), (ck, cd) in zip(succ, csucc):
-            assert list(kk) == ck and R.state_to_json(t) == cd, (name, kk, ck)
-        perm = list(range(n))
-        rng.shuffle(perm)
-        pv = R.permute_view(st.view(), perm)
-        inv = [0] * n
-        for a in range(n):
-            inv[perm[a]] = a
-        pst = R.State(votedFor=pv[0], currentTerm=pv[1], logs=pv[2], matchIndex=pv[3], nextIndex=pv[4],
-                      commitIndex=pv[5], msgs=frozenset(pv[6]), role=pv[7], electionCount=st.electionCount,
-                      restartCount=st.restartCount,
-                      pendingResponse=tuple(tuple(st.pendingResponse[inv[a]][inv[b]] for b in range(n))
-                                            for a in range(n)),
-                      valSent=st.valSent)
-        assert R.canonical(cfg, pst) == R.canonical(cfg, st)
-        sjs = []
-        for kk, t in succ:
-            tj = R.state_to_json(t)
-            c = R.canonical(cfg, t)
-            cid = canon_ids.setdefault(c, len(canon_ids))
-            ch = c_canon(lib, cfg, tj)
-            assert c_of_py.setdefault(ch, cid) == cid, (name, "C/Python canonical partitions differ")
-            sjs.append(dict(key=list(kk), state=tj, canon=cid))
-        invs = {}
-        for sc_st, sc_d, tag in [(st, d, "state")] + [(t, R.state_to_json(t), f"succ{j}")
-                                                     for j, (_, t) in enumerate(succ[:4])]:
-            vals = []
-            for ii, nm in enumerate(INV_NAMES):
-                try:
-                    pyv = R.INV_FUNCS[nm](cfg, sc_st)
-                except R.EvalError:
-                    pyv = None
-                assert c_inv(lib, cfg, sc_d, ii) == pyv, (name, nm, tag)
-                vals.append(pyv)
-            invs[tag] = vals
-        items.append(dict(depth=abs(k), synthetic=k < 0, nmsgs=len(st.msgs), assert_fails=False, state=d, permuted=R.state_to_json(pst),
-                          successors=sjs, invariants=invs))
+        items.append(state_record(lib, cfg, name, rng, k, st, canon_ids, c_of_py))
     nm = [it["nmsgs"] for it in items if not it["synthetic"]]
     succ_nm = [len(s["state"]["msgs"]) for it in items for s in it.get("successors", [])]
     out = dict(n=n, V=V, E=E, R=Rr, items=items,

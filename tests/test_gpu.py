@@ -102,12 +102,9 @@ INV_NAMES = ["Inv", "NoSplitVote", "RaftCanCommt", "FollowerCanCommit", "CommitA
              "ExistLeaderAndCandidate"]
 
 
-@pytest.mark.parametrize("name", sorted(DEEP))
-def test_deep_successors_match_oracle(name):
-    """Successor lists (TLC order, keys and concrete states) of message-heavy states, and the Assert
-    (tla:185) exactly where both oracles raise it."""
-    g = DEEP[name]
-    mc = checker(g["n"], g["V"], g["E"], g["R"])
+def check_deep_successors(g, mc):
+    """Successor lists (TLC order, keys and concrete states) of a deep-format fixture configuration, and
+    the Assert (tla:185) exactly where both oracles raise it."""
     n_assert = 0
     for it in g["items"]:
         if it["assert_fails"]:
@@ -123,12 +120,9 @@ def test_deep_successors_match_oracle(name):
     assert n_assert == g["coverage"]["assert_states"]
 
 
-@pytest.mark.parametrize("name", sorted(DEEP))
-def test_deep_fingerprint_classes_match_oracle(name):
+def check_deep_fingerprint_classes(g, mc):
     """The 128-bit symmetry fingerprint induces the oracles' exact canonical partition on every
-    successor of the deep states (and a permuted copy has its state's fingerprint)."""
-    g = DEEP[name]
-    mc = checker(g["n"], g["V"], g["E"], g["R"])
+    successor of the fixture's states (and a permuted copy has its state's fingerprint)."""
     fp_of_canon, canon_of_fp = {}, {}
     for it in g["items"]:
         if it["assert_fails"]:
@@ -141,18 +135,39 @@ def test_deep_fingerprint_classes_match_oracle(name):
     assert len(fp_of_canon) == len({e["canon"] for it in g["items"] for e in it.get("successors", [])})
 
 
-@pytest.mark.parametrize("name", sorted(DEEP))
-def test_deep_invariants_match_oracle(name):
-    """Every invariant (tla:434-499; None = TLC evaluation error) on the deep states and their first
+def check_deep_invariants(g, mc):
+    """Every invariant (tla:434-499; None = TLC evaluation error) on the fixture's states and their first
     successors, as both oracles evaluate them."""
-    g = DEEP[name]
-    mc = checker(g["n"], g["V"], g["E"], g["R"])
     for it in g["items"]:
         if it["assert_fails"]:
             continue
         for tag, vals in it["invariants"].items():
             st = it["state"] if tag == "state" else it["successors"][int(tag[4:])]["state"]
             assert [mc.eval_invariant(st, nm) for nm in INV_NAMES] == vals, (tag, it["nmsgs"])
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_successors_match_oracle(name):
+    """Successor lists (TLC order, keys and concrete states) of message-heavy states, and the Assert
+    (tla:185) exactly where both oracles raise it."""
+    g = DEEP[name]
+    check_deep_successors(g, checker(g["n"], g["V"], g["E"], g["R"]))
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_fingerprint_classes_match_oracle(name):
+    """The 128-bit symmetry fingerprint induces the oracles' exact canonical partition on every
+    successor of the deep states (and a permuted copy has its state's fingerprint)."""
+    g = DEEP[name]
+    check_deep_fingerprint_classes(g, checker(g["n"], g["V"], g["E"], g["R"]))
+
+
+@pytest.mark.parametrize("name", sorted(DEEP))
+def test_deep_invariants_match_oracle(name):
+    """Every invariant (tla:434-499; None = TLC evaluation error) on the deep states and their first
+    successors, as both oracles evaluate them."""
+    g = DEEP[name]
+    check_deep_invariants(g, checker(g["n"], g["V"], g["E"], g["R"]))
 
 
 def _no_all_commit_state(msgs):
@@ -897,15 +912,9 @@ def _trace_matches(mc, t):
     assert [(list(k) if k else None, st) for k, st in mc.trace()] == [(e["key"], e["state"]) for e in t["steps"]]
 
 
-@pytest.mark.parametrize("mode", ["default", "host_levels", "split", "virtual2", "virtual4", "rccl1"])
-@pytest.mark.parametrize("name", sorted(LEVELS_ERR))
-def test_bfs_error_precedence_matches_golden(name, mode, monkeypatch):
-    """The Assert (Raft.tla:185) and Inv's evaluation error (Raft.tla:499) met inside a BFS -- the test
-    variants RaftSplitBrain / RaftCommitPastLog -- stop the run where both oracles stop it: the same
-    verdict, TLC's counters at the error (states generated and distinct, queue left), the levels before
-    it and the counterexample, on the device loop, host-driven levels, split chunks, 2/4 virtual shards
-    and the one-rank RCCL communicator."""
-    g = LEVELS_ERR[name]
+def mode_kwargs(mode, monkeypatch):
+    """ModelConfig arguments (and environment) of an execution mode: the device loop (`default`), host-driven
+    levels, split chunks, k virtual shards (`virtual<k>`), the one-rank RCCL communicator."""
     kw = {}
     if mode == "host_levels":
         kw = dict(device_levels=1)
@@ -917,7 +926,19 @@ def test_bfs_error_precedence_matches_golden(name, mode, monkeypatch):
     elif mode == "rccl1":
         kw = dict(world_size=1, rank=0, comm_unique_id=raftmc.comm_unique_id(), chunk_successors=3000,
                   shard_min_states=1)
-    mc, res = run_cfg(g, **kw)
+    return kw
+
+
+@pytest.mark.parametrize("mode", ["default", "host_levels", "split", "virtual2", "virtual4", "rccl1"])
+@pytest.mark.parametrize("name", sorted(LEVELS_ERR))
+def test_bfs_error_precedence_matches_golden(name, mode, monkeypatch):
+    """The Assert (Raft.tla:185) and Inv's evaluation error (Raft.tla:499) met inside a BFS -- the test
+    variants RaftSplitBrain / RaftCommitPastLog -- stop the run where both oracles stop it: the same
+    verdict, TLC's counters at the error (states generated and distinct, queue left), the levels before
+    it and the counterexample, on the device loop, host-driven levels, split chunks, 2/4 virtual shards
+    and the one-rank RCCL communicator."""
+    g = LEVELS_ERR[name]
+    mc, res = run_cfg(g, **mode_kwargs(mode, monkeypatch))
     check_levels(g, res)
     assert [ls.new_states for ls in res.levels if ls.new_states][:len(g["levels"]) - 1] == g["levels"][:-1]
     _trace_matches(mc, TRACES_ERR[name])

@@ -39,7 +39,7 @@ SAMPLES = 10_000
 LO, HI = 35, 72
 
 
-def _images(u):
+def _images(u, N=N, V=V, E=E, RR=RR):
     """(vi): the state's server-permuted images and a copy with its non-VIEW variables changed (unpacked)."""
     st = R.state_from_json(raftmc.unpacked_to_state(list(u), N, V))
     out = []
@@ -69,85 +69,93 @@ def _orc():
     return lib
 
 
-def test_raft_cfg_deep_levels_sampled():
+def check_sampled_levels(mc, res, N, V, E, RR, LO, HI, SAMPLES, seed, msg_cap=64):
+    """Checks (i)-(vi) of this file's docstring on SAMPLES states drawn evenly (seeded) from levels LO..HI of
+    the finished run `res` of checker `mc`, with oracle/raft_oracle.c as the checker.  Returns the numbers
+    of sampled states, of oracle successors looked up and of images fingerprinted."""
     lib = _orc()
-    stride = raftmc.unpacked_len(N, V, 64)
-    cfg = raftmc.ModelConfig(n_servers=N, n_vals=V, max_election=E, max_restart=RR)
+    stride = raftmc.unpacked_len(N, V, msg_cap)
     init_u = raftmc.state_to_unpacked(R.state_to_json(R.init_state(R.Config(n=N, V=V, max_election=E,
                                                                              max_restart=RR))), N, V)
     init_arr = (ctypes.c_int32 * stride)(*init_u)
+    size = {1: 1}
+    for ls in res.levels:
+        if ls.new_states:
+            size[ls.level + 1] = ls.new_states
+    start, at = {}, 0
+    for L in sorted(size):
+        start[L] = at
+        at += size[L]
+    assert at == res.distinct
+    # an even share per level; what the last, small levels cannot take goes to the widest ones
+    per = -(-SAMPLES // (HI - LO + 1))
+    quota = {L: min(per, size[L]) for L in range(LO, HI + 1)}
+    short = SAMPLES - sum(quota.values())
+    for L in sorted(quota, key=lambda x: -size[x]):
+        add = min(short, size[L] - quota[L])
+        quota[L] += add
+        short -= add
+    rng = random.Random(seed)
+    picks = sorted((L, start[L] + i) for L in quota for i in rng.sample(range(size[L]), quota[L]))
+    out = (ctypes.c_int32 * stride)()
+    par = (ctypes.c_int32 * stride)()
+    succ = (ctypes.c_int32 * (stride * 512))()
+    skeys = (ctypes.c_uint32 * 512)()
+    h = (ctypes.c_uint64 * 2)()
+    batch, classes, n_succ = [], set(), 0
+    images, owner = [], []  # (vi): each image and the batch index of its state
+    for L, gid in picks:
+        keys, gids = mc.state_path(gid)
+        # (i) L - 1 steps, through the levels in order
+        assert len(keys) == L - 1 and gids[-1] == gid, (L, gid)
+        for k, g in enumerate(gids):
+            assert start[k + 1] <= g < start[k + 1] + size[k + 1], (L, gid, k, g)
+        ck = (ctypes.c_uint32 * len(keys))(*[(s << 24) | (a << 16) | w for s, a, w in keys])
+        r = lib.orc_replay(N, V, E, RR, 0, init_arr, ck, len(keys), out, stride)
+        assert r > 0, f"level {L} state {gid}: step {-r} of its path is not enabled in the oracle"
+        # (iii) first discovery wins among its parent's successors
+        assert lib.orc_replay(N, V, E, RR, 0, init_arr, ck, len(keys) - 1, par, stride) > 0
+        ns = lib.orc_successors(N, V, E, RR, 0, par, succ, stride, 512, skeys)
+        assert ns > 0
+        j = next(i for i in range(ns) if skeys[i] == ck[len(keys) - 1])
+        assert list(succ[j * stride:j * stride + r]) == list(out[:r])
+        assert lib.orc_canon_hash(N, V, out, h) == 0
+        mine = (h[0], h[1])
+        for i in range(j):
+            assert lib.orc_canon_hash(N, V, ctypes.cast(ctypes.addressof(succ) + 4 * i * stride,
+                                                        ctypes.POINTER(ctypes.c_int32)), h) == 0
+            assert (h[0], h[1]) != mine, f"level {L} state {gid}: an earlier successor of its parent is in its class"
+        # (iv) one state per class
+        assert mine not in classes, f"level {L} state {gid}: a second state of one symmetry class"
+        classes.add(mine)
+        # (ii) + (v): the state and every oracle successor of it
+        for img in _images(out[:r], N, V, E, RR):
+            images.append(np.asarray(img + [0] * (stride - len(img)), dtype=np.int32))
+            owner.append(len(batch))
+        batch.append(np.frombuffer(out, dtype=np.int32, count=stride).copy())
+        ns = lib.orc_successors(N, V, E, RR, 0, out, succ, stride, 512, skeys)
+        assert ns >= 0
+        n_succ += ns
+        for i in range(ns):
+            batch.append(np.frombuffer(succ, dtype=np.int32, count=stride, offset=4 * i * stride).copy())
+    arr = np.ascontiguousarray(np.stack(batch))
+    fps = mc.fingerprints_unpacked(arr, stride, len(batch))
+    present = mc.seen_contains(fps)
+    missing = sum(1 for p in present if not p)
+    assert missing == 0, f"{missing} of {len(batch)} sampled states / oracle successors not in the seen set"
+    # (vi) the images' fingerprints are their states'
+    ifp = mc.fingerprints_unpacked(np.ascontiguousarray(np.stack(images)), stride, len(images))
+    split = sum(1 for k, f in enumerate(ifp) if tuple(f) != tuple(fps[owner[k]]))
+    assert split == 0, f"{split} of {len(images)} symmetric / non-VIEW images fingerprint apart from their states"
+    return len(picks), n_succ, len(images)
+
+
+def test_raft_cfg_deep_levels_sampled():
+    cfg = raftmc.ModelConfig(n_servers=N, n_vals=V, max_election=E, max_restart=RR)
     with raftmc.ModelChecker(cfg) as mc:
         res = mc.run()
         assert res.status == "done" and res.depth == HI
-        size = {1: 1}
-        for ls in res.levels:
-            if ls.new_states:
-                size[ls.level + 1] = ls.new_states
-        start, at = {}, 0
-        for L in sorted(size):
-            start[L] = at
-            at += size[L]
-        assert at == res.distinct
-        # an even share per level; what the last, small levels cannot take goes to the widest ones
-        per = -(-SAMPLES // (HI - LO + 1))
-        quota = {L: min(per, size[L]) for L in range(LO, HI + 1)}
-        short = SAMPLES - sum(quota.values())
-        for L in sorted(quota, key=lambda x: -size[x]):
-            add = min(short, size[L] - quota[L])
-            quota[L] += add
-            short -= add
-        rng = random.Random(20261017)
-        picks = sorted((L, start[L] + i) for L in quota for i in rng.sample(range(size[L]), quota[L]))
-        out = (ctypes.c_int32 * stride)()
-        par = (ctypes.c_int32 * stride)()
-        succ = (ctypes.c_int32 * (stride * 512))()
-        skeys = (ctypes.c_uint32 * 512)()
-        h = (ctypes.c_uint64 * 2)()
-        batch, classes, n_succ = [], set(), 0
-        images, owner = [], []  # (vi): each image and the batch index of its state
-        for L, gid in picks:
-            keys, gids = mc.state_path(gid)
-            # (i) L - 1 steps, through the levels in order
-            assert len(keys) == L - 1 and gids[-1] == gid, (L, gid)
-            for k, g in enumerate(gids):
-                assert start[k + 1] <= g < start[k + 1] + size[k + 1], (L, gid, k, g)
-            ck = (ctypes.c_uint32 * len(keys))(*[(s << 24) | (a << 16) | w for s, a, w in keys])
-            r = lib.orc_replay(N, V, E, RR, 0, init_arr, ck, len(keys), out, stride)
-            assert r > 0, f"level {L} state {gid}: step {-r} of its path is not enabled in the oracle"
-            # (iii) first discovery wins among its parent's successors
-            assert lib.orc_replay(N, V, E, RR, 0, init_arr, ck, len(keys) - 1, par, stride) > 0
-            ns = lib.orc_successors(N, V, E, RR, 0, par, succ, stride, 512, skeys)
-            assert ns > 0
-            j = next(i for i in range(ns) if skeys[i] == ck[len(keys) - 1])
-            assert list(succ[j * stride:j * stride + r]) == list(out[:r])
-            assert lib.orc_canon_hash(N, V, out, h) == 0
-            mine = (h[0], h[1])
-            for i in range(j):
-                assert lib.orc_canon_hash(N, V, ctypes.cast(ctypes.addressof(succ) + 4 * i * stride,
-                                                            ctypes.POINTER(ctypes.c_int32)), h) == 0
-                assert (h[0], h[1]) != mine, f"level {L} state {gid}: an earlier successor of its parent is in its class"
-            # (iv) one state per class
-            assert mine not in classes, f"level {L} state {gid}: a second state of one symmetry class"
-            classes.add(mine)
-            # (ii) + (v): the state and every oracle successor of it
-            for img in _images(out[:r]):
-                images.append(np.asarray(img + [0] * (stride - len(img)), dtype=np.int32))
-                owner.append(len(batch))
-            batch.append(np.frombuffer(out, dtype=np.int32, count=stride).copy())
-            ns = lib.orc_successors(N, V, E, RR, 0, out, succ, stride, 512, skeys)
-            assert ns >= 0
-            n_succ += ns
-            for i in range(ns):
-                batch.append(np.frombuffer(succ, dtype=np.int32, count=stride, offset=4 * i * stride).copy())
-        arr = np.ascontiguousarray(np.stack(batch))
-        fps = mc.fingerprints_unpacked(arr, stride, len(batch))
-        present = mc.seen_contains(fps)
-        missing = sum(1 for p in present if not p)
-        assert missing == 0, f"{missing} of {len(batch)} sampled states / oracle successors not in the seen set"
-        # (vi) the images' fingerprints are their states'
-        ifp = mc.fingerprints_unpacked(np.ascontiguousarray(np.stack(images)), stride, len(images))
-        split = sum(1 for k, f in enumerate(ifp) if tuple(f) != tuple(fps[owner[k]]))
-        assert split == 0, f"{split} of {len(images)} symmetric / non-VIEW images fingerprint apart from their states"
-    print(f"deep check: {len(picks)} states over levels {LO}-{HI}, {n_succ} oracle successors, all in the seen set; "
-          f"{len(images)} images, each with its state's fingerprint")
-    assert len(picks) == SAMPLES
+        n_picks, n_succ, n_images = check_sampled_levels(mc, res, N, V, E, RR, LO, HI, SAMPLES, 20261017)
+    print(f"deep check: {n_picks} states over levels {LO}-{HI}, {n_succ} oracle successors, all in the seen set; "
+          f"{n_images} images, each with its state's fingerprint")
+    assert n_picks == SAMPLES

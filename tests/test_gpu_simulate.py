@@ -85,6 +85,11 @@ PARITY = {
     "bf_n4_v1_e1_r3": (dict(n=4, V=1, E=1, Rr=3, variant="become_follower"), 50, 100, 1),
     "n5_v1_e3_r3": (dict(n=5, V=1, E=3, Rr=3), 60, 200, 1),
     "bf_n5_v2_e3_r3": (dict(n=5, V=2, E=3, Rr=3, variant="become_follower"), 30, 200, 1),
+    # MaxElection / MaxRestart past 3: terms, election and restart counters up to 7 inside k_walk
+    "n3_v1_e7_r7": (dict(n=3, V=1, E=7, Rr=7), 200, 100, 1),
+    "n3_v2_e6_r6": (dict(n=3, V=2, E=6, Rr=6), 200, 100, 1),
+    "n5_v1_e7_r7": (dict(n=5, V=1, E=7, Rr=7), 200, 100, 1),
+    "bf_n3_v1_e7_r7": (dict(n=3, V=1, E=7, Rr=7, variant="become_follower"), 200, 100, 1),
 }
 
 

@@ -5,6 +5,7 @@
 // by content (FNV-1a 64 of the text with CRLF normalised) -- the shipped Raft.tla or
 // the seeded variant produced by tools/make_seeded_spec.py.  Pure CPU code.
 #include "rmc_cfg.h"
+#include "rmc_spec.h"
 
 #include <algorithm>
 #include <cctype>
@@ -257,6 +258,16 @@ bool parse_model(const std::string &cfg_text, const char *tla_text, ParsedModel 
     if (!need_set("Vals", &pm->vals, 0, 3)) return false;
     pm->cfg.n_servers = (int32_t)pm->servers.size();
     pm->cfg.n_vals = (int32_t)pm->vals.size();
+    // the message universe of (|Servers|, |Vals|, MaxElection) must fit the 16-bit message ids (rmc_spec.h):
+    // rmc_create would refuse it, so the cfg is refused before a device is opened
+    if (pm->cfg.max_election > max_election_limit(pm->cfg.n_servers, pm->cfg.n_vals)) {
+        err = "CONSTANT MaxElection = " + std::to_string(pm->cfg.max_election) + " is too large for " +
+              std::to_string(pm->cfg.n_servers) + " servers and " + std::to_string(pm->cfg.n_vals) + " values (" +
+              std::to_string(make_dims(pm->cfg.n_servers, pm->cfg.n_vals, pm->cfg.max_election).total) +
+              " message records, past the 16-bit message ids): MaxElection is at most " +
+              std::to_string(max_election_limit(pm->cfg.n_servers, pm->cfg.n_vals)) + " for this pair";
+        return false;
+    }
     pm->cfg.no_symmetry = pm->symmetry ? 0 : 1;
     pm->cfg.world_size = 1;
     pm->cfg.device = -1;

@@ -111,7 +111,8 @@ struct Universe {
                     }
                 }
         if (items.size() != d.total) throw Fail(RMC_E_ARG, "message universe size mismatch");
-        if (items.size() >= 0xFFFF) throw Fail(RMC_E_CAPACITY, "message universe exceeds 16-bit ids");
+        // (setup() refuses such a configuration with RMC_E_ARG before it gets here)
+        if (items.size() >= MSG_ID_LIMIT) throw Fail(RMC_E_STATE, "internal: message universe exceeds 16-bit ids");
         std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.key < b.key; });
         info.resize(items.size());
         gmsg.resize(items.size());
@@ -1233,6 +1234,13 @@ struct rmc_ctx {
         if (cfg.max_election < 0 || cfg.max_election > 7) throw Fail(RMC_E_ARG, "max_election must be 0..7");
         if (cfg.max_restart < 0 || cfg.max_restart > 15) throw Fail(RMC_E_ARG, "max_restart must be 0..15");
         if (cfg.invariants & ~0x7Fu) throw Fail(RMC_E_ARG, "unknown invariant bits");
+        // the message universe must fit the 16-bit ids (host arithmetic: nothing has touched the device yet)
+        if (cfg.max_election > max_election_limit(cfg.n_servers, cfg.n_vals))
+            throw Fail(RMC_E_ARG, "max_election=" + std::to_string(cfg.max_election) + " with n_servers=" +
+                                      std::to_string(cfg.n_servers) + " n_vals=" + std::to_string(cfg.n_vals) + " needs " +
+                                      std::to_string(make_dims(cfg.n_servers, cfg.n_vals, cfg.max_election).total) +
+                                      " message records, past the 16-bit message ids: max_election is at most " +
+                                      std::to_string(max_election_limit(cfg.n_servers, cfg.n_vals)) + " for this pair");
         // invariant order: the cfg's, else bit order; every listed invariant must be selected
         inv_order = 0;
         if (cfg.invariant_order) {
@@ -4495,6 +4503,8 @@ int rmc_comm_unique_id(void *out128) {
 #endif
 }
 
+static thread_local std::string g_create_err = "null context";  // the calling thread's last failed rmc_create
+
 int rmc_create(const rmc_config *cfg, void **out) {
     if (!cfg || !out) return RMC_E_ARG;
     *out = nullptr;
@@ -4507,6 +4517,7 @@ int rmc_create(const rmc_config *cfg, void **out) {
     });
     if (rc != RMC_OK) {
         std::fprintf(stderr, "rmc_create: %s\n", c->err.c_str());
+        g_create_err = c->err;  // rmc_last_error(NULL): there is no context to ask
         c->release();
         delete c;
         return rc;
@@ -4837,7 +4848,7 @@ int rmc_trace_state(void *ctx, uint32_t i, int32_t *unpacked, size_t cap, int32_
 
 const char *rmc_last_error(void *ctx) {
     rmc_ctx *c = (rmc_ctx *)ctx;
-    return c ? c->err.c_str() : "null context";
+    return c ? c->err.c_str() : g_create_err.c_str();
 }
 
 void rmc_destroy(void *ctx) {

@@ -227,6 +227,16 @@ RMC_HD Dims make_dims(int n, int V, int E) {
     return d;
 }
 
+// Message ids are 16 bit and 0xFFFF means "none" (Universe::nat2id, KEY_NONE's width): the universe
+// must hold fewer records than that.  The largest MaxElection (cfg:4, at most 7) whose universe does,
+// for n servers and V values: 7 for one value at any n and for (2,2); (3,2) 6, (3,3) 4, (4,2) 5, (5,2) 4.
+constexpr uint32_t MSG_ID_LIMIT = 0xFFFFu;
+RMC_HD int max_election_limit(int n, int V) {
+    int E = 7;
+    while (E > 0 && make_dims(n, V, E).total >= MSG_ID_LIMIT) E--;
+    return E;
+}
+
 // term >= 1 for every message (terms of sent messages are currentTerm values after
 // at least one election, tla:111,121).
 RMC_HD uint32_t nat_vreq(const Dims &d, uint32_t src, uint32_t dst, uint32_t term, uint32_t lli, uint32_t llt) {

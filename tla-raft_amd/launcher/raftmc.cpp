@@ -799,7 +799,7 @@ int main(int argc, char **argv) {
         ::close(saved_out);
     }
     phase_time("created");
-    if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d)\n", rc); return 75; }
+    if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d): %s\n", rc, rmc_last_error(nullptr)); return 75; }
     rmc_level_stats st;
     if (coverage && rmc_set_coverage(ctx, 1) < 0) {
         std::printf("Error: %s\n", rmc_last_error(ctx));
@@ -1043,7 +1043,7 @@ int main(int argc, char **argv) {
         const auto t0 = std::chrono::steady_clock::now();
         void *ctx = nullptr;
         int rc = rmc_create(&cfg, &ctx);
-        if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d)\n", rc); return 75; }
+        if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d): %s\n", rc, rmc_last_error(nullptr)); return 75; }
         rmc_sim_config sc{};
         sc.num_walks = sim_num;
         sc.seed = sim_seed;

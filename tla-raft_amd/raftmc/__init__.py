@@ -611,7 +611,7 @@ class ModelChecker:
         h = ctypes.c_void_p()
         rc = self.lib.rmc_create(ctypes.byref(self._c), ctypes.byref(h))
         if rc != RMC_OK:
-            raise RmcError(f"rmc_create failed: {ERRORS.get(rc, rc)} (see stderr)")
+            raise RmcError(f"rmc_create failed: {ERRORS.get(rc, rc)}: {self.lib.rmc_last_error(None).decode()}")
         self.h = h
         self.levels: List[LevelStats] = []
         self._inited = False
