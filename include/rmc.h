@@ -525,7 +525,8 @@ int rmc_fingerprint(void *ctx, const int32_t *unpacked, uint64_t fp[2]);
 /* ABI 4 -- checks of a finished run's deep levels (tests/test_gpu_deep.py).  The path of the explored
  * state with global id `gid` (BFS order, Init = 0): len = its depth, keys[i] = how state i of the path
  * was reached from state i - 1 (rmc_successors' key format; keys[0] = 0), gids[i] = its global id
- * (gids[0] = 0, gids[len - 1] = gid); from TLC's parent pointers (the trace), any shard layout. */
+ * (gids[0] = the initial state the path starts at: 0, Init, unless the run was seeded with rmc_init_from,
+ * then the root's id; gids[len - 1] = gid); from TLC's parent pointers (the trace), any shard layout. */
 int rmc_state_path(void *ctx, uint64_t gid, uint32_t *keys, uint64_t *gids, uint32_t cap, uint32_t *len);
 /* Fingerprints of n unpacked states, stride_ints apart (2 words each), in one launch. */
 int rmc_fingerprints(void *ctx, const int32_t *unpacked, size_t stride_ints, uint64_t n, uint64_t *fps);
@@ -540,6 +541,25 @@ int rmc_eval_invariant(void *ctx, const int32_t *unpacked, uint32_t invariant_bi
  * It is one level as far as rmc_graph_reach_levels is concerned; the next rmc_init or rmc_reset drops it. */
 int rmc_graph_import(void *ctx, uint64_t n_states, uint64_t n_edges, const uint32_t *src, const uint32_t *dst,
                      const uint16_t *inv_values);
+/* Test hook, called in place of rmc_init: a level of given states stands where Init's would, so that tests
+ * reach the search's batch kernels with states no test search gets to (msgs only grows, Raft.tla:43-45: the
+ * message-heavy states lie deep).  It is TLC's behaviour with several initial states.  n (1..65,536) unpacked
+ * states, stride_ints apart; a field out of range is RMC_E_ARG, more messages than the lanes RMC_E_CAPACITY.
+ * The first state of each SYMMETRY/VIEW class in argument order is kept: the m kept roots get global ids
+ * 0 .. m - 1 in that order, have no parent, and are level 1 (total_generated = n, total_distinct = m, depth 1,
+ * queue m).  The INVARIANTs are evaluated on the roots in order; the first root that fails gives the verdict
+ * Init would give, with a one-state trace holding that root (continuation counts violating roots at level 1).
+ * Only each field's range is checked: a state no run reaches may still leave the kernels' domain later -- one at
+ * term MaxElection with elections left sends, after BecomeCandidate, VoteReqs of a term the static message
+ * universe does not hold (in a reachable state no term is past electionCount); the caller keeps its roots clear
+ * of that over the levels it runs.  Everything after the call is the unchanged search.  Traces, rmc_state_path and rmc_violation_trace end at a
+ * root; coverage's Init entry is (m, n); graph mode and keep deliver the roots as level 1, without edges.
+ * rmc_reset returns to "before init": a following rmc_init starts from the real Init, a following
+ * rmc_init_from seeds again.  rmc_simulate is untouched (walks start at Init).  Virtual shards take it when
+ * the run starts replicated (shard_min_states > m; the roots stand on shard 0, as Init does); RCCL ranks, the
+ * host-staged transport and shard_min_states <= m are refused with RMC_E_STATE, and so is rmc_checkpoint of a
+ * seeded run (the file format has no place for the roots). */
+int rmc_init_from(void *ctx, const int32_t *unpacked, size_t stride_ints, uint64_t n, rmc_level_stats *st);
 
 /* Unpacked state (int32), the interchange format of every hook:
  *   votedFor[n] (-1 = None)  currentTerm[n]  role[n] (0 F, 1 C, 2 L)  commitIndex[n]  logLen[n]

@@ -28,6 +28,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -2211,6 +2212,160 @@ struct rmc_ctx {
         return init_verdict(iv, rw, t0, st);
     }
 
+    // ---- test hook (rmc_init_from): a level of given states in place of Init's ------------------
+    // TLC with several initial states: the first state of each SYMMETRY/VIEW class, in argument order,
+    // becomes a root (global ids 0 .. m - 1, no parent), the roots stand in shard 0's ring as level 1 and
+    // in its seen set, and the ordinary search goes on from there.  Init's cached record, fingerprint and
+    // verdicts (init_cached) are not touched: rmc_reset + rmc_init start from the real Init again.  The
+    // roots' records stay on the host, because a counterexample of a seeded run is replayed from its root.
+    std::vector<uint32_t> roots;        // the kept roots' records, RECW words each (empty: the run began at Init)
+    uint64_t seed_n = 1, seed_m = 1;    // initial states given / kept (coverage's Init entry)
+    int init_from(const int32_t *u, size_t stride, uint64_t n, rmc_level_stats *st) {
+        if (inited) throw Fail(RMC_E_STATE, "rmc_init_from: the run has begun (rmc_reset first)");
+        if (!u || n < 1 || n > 65536) throw Fail(RMC_E_ARG, "rmc_init_from: 1 to 65,536 states");
+        if (rccl) throw Fail(RMC_E_STATE, "rmc_init_from: not with RCCL ranks (the roots would have to be agreed between processes)");
+        if (hostx) throw Fail(RMC_E_STATE, "rmc_init_from: not with the host-staged transport (the roots would have to be agreed between processes)");
+        const size_t head = RMC_UNPACKED_INTS(N, V, 0);
+        if (stride < head) throw Fail(RMC_E_ARG, "rmc_init_from: stride too small");
+        std::vector<uint32_t> rec((size_t)n * RECW);
+        for (uint64_t i = 0; i < n; i++) {
+            const int32_t *ui = u + i * stride;
+            const int32_t nm = ui[head - 1];
+            if (nm < 0) throw Fail(RMC_E_ARG, "rmc_init_from: negative message count");
+            if (nm > ks.MCAP) throw Fail(RMC_E_CAPACITY, "state has more messages than msg_cap");
+            if ((size_t)RMC_UNPACKED_INTS(N, V, nm) > stride) throw Fail(RMC_E_ARG, "rmc_init_from: stride too small");
+            pack(ui, rec.data() + i * RECW);
+        }
+        auto t0 = std::chrono::steady_clock::now();
+        struct Tmp {
+            uint32_t *rec = nullptr;
+            ulonglong2 *fp = nullptr;
+            int32_t *iv = nullptr;
+            ~Tmp() { dfree(rec); dfree(fp); dfree(iv); }
+        } d;
+        d.rec = dmalloc<uint32_t>(rec.size());
+        d.fp = dmalloc<ulonglong2>(n);
+        d.iv = dmalloc<int32_t>(7 * n);
+        Shard &s = sh[0];
+        KParams P = base(s);
+        P.front = d.rec;
+        P.fp = d.fp;
+        HIPCHK(hipMemcpyAsync(d.rec, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, stream));
+        ks.fp_states(P, n, stream);
+        std::vector<ulonglong2> fps(n);
+        HIPCHK(hipMemcpyAsync(fps.data(), d.fp, n * 16, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        // the first state of each class, in argument order
+        std::set<std::pair<uint64_t, uint64_t>> classes;
+        std::vector<uint32_t> krec, ring;
+        std::vector<uint64_t> off;
+        std::vector<ulonglong2> kfp;
+        for (uint64_t i = 0; i < n; i++) {
+            if (!classes.insert({fps[i].x, fps[i].y}).second) continue;
+            const uint32_t *r = rec.data() + i * RECW;
+            krec.insert(krec.end(), r, r + RECW);
+            off.push_back(ring.size());
+            ring.insert(ring.end(), r, r + record_words(r));
+            kfp.push_back(fps[i]);
+        }
+        const uint64_t m = kfp.size(), words = ring.size();
+        if (multi && shard_min <= m)
+            throw Fail(RMC_E_STATE, "rmc_init_from: " + std::to_string(m) + " roots with shard_min_states = " +
+                                        std::to_string(shard_min) + ": the roots stand on shard 0 like Init, so the run must "
+                                        "start replicated (shard_min_states above the number of roots)");
+        if (coverage) cov_alloc();
+        if (cont) viol_alloc();
+        viol_flag();
+        replicated = multi;
+        for (Shard &t : sh) {
+            t.level_start = {0};
+            t.cur_n = t.nxt_n = 0;
+            t.cur_wbase = t.cur_words = t.nxt_words = 0;
+        }
+        // sized as for a level of m states: seen set, ring, offsets (the host trace arrays grow by themselves)
+        grow_seen(s, m);
+        ensure_ring(s, words, 0);
+        ensure_off(s.cur_off, s.cur_off_cap, 0, m);
+        HIPCHK(hipMemcpyAsync(s.R, ring.data(), words * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(s.cur_off, off.data(), m * 8, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d.rec, krec.data(), krec.size() * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d.fp, kfp.data(), m * 16, hipMemcpyHostToDevice, stream));
+        launch_insert_fps(d.fp, m, s.seen(), stream);
+        ks.inv_states(P, m, d.iv, stream);
+        std::vector<int32_t> iv(7 * m);
+        HIPCHK(hipMemcpyAsync(iv.data(), d.iv, iv.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        for (uint64_t g = 0; g < m; g++) {
+            s.hpar.set(g, ~0ull);
+            s.hslot.set(g, 0);
+        }
+        s.tflushed = m;
+        s.cur_n = m;
+        s.cur_words = words;
+        s.T_count = m;
+        s.peak_words = std::max(s.peak_words, words);
+        roots = std::move(krec);
+        seed_n = n;
+        seed_m = m;
+        if (gkeep) {
+            kept.clear();
+            kept_imported = false;
+        }
+        total_generated = n;
+        total_distinct = m;
+        depth = 1;
+        inited = true;
+        status = RMC_OK;
+        if (graph) {  // the roots are level 1 of the graph: into the gid map and to the sink, no edges
+            graph_alloc();
+            try {
+                graph_states(s, s.cur_off, s.cur_wbase, m, 0);
+            } catch (const Fail &e) {
+                finished = true;
+                status = e.code;
+                throw;
+            }
+        }
+        // the roots' invariants in order, each root's in cfg order (init_verdict, per root)
+        if (cont) viol_rows.assign(1, std::array<uint64_t, VN>{});
+        for (uint64_t g = 0; g < m && !finished; g++)
+            for (uint32_t o = inv_order; o; o >>= 4) {
+                const int b = (int)(o & 15u) - 1;
+                const int32_t v = iv[7 * g + b];
+                if (v == 0 && cont) {
+                    viol_rows[0][b]++;
+                    if (viol_first[b] == ~0ull) {
+                        viol_first[b] = g;
+                        viol_first_level[b] = 1;
+                    }
+                    break;
+                }
+                if (v != 1) {
+                    status = v == 0 ? RMC_VIOLATION : RMC_EVAL_ERROR;
+                    violated = b;
+                    err_ref = g;
+                    err_last_slot = KEY_NONE;
+                    queue_at_end = 0;
+                    finished = true;
+                    build_trace();
+                    break;
+                }
+            }
+        seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (st) {
+            std::memset(st, 0, sizeof *st);
+            st->level = 1;
+            st->status = status;
+            st->total_generated = total_generated;
+            st->total_distinct = total_distinct;
+            st->queue = finished ? 0 : m;
+            st->new_states = m;
+            st->seconds = seconds;
+            st->new_bytes = words * 4;
+        }
+        return status;
+    }
+
     // First Init of the run (or every Init of a sharded run): record, fingerprint and invariants
     // on the device; the single-GPU path caches them for later runs (rmc_reset).
     void init_full(const std::vector<uint32_t> &rec, uint32_t rw, int32_t *iv) {
@@ -3870,17 +4025,22 @@ struct rmc_ctx {
         return slots;
     }
 
-    void build_trace() {
-        std::vector<uint16_t> slots = path_slots(err_ref, nullptr);
-        if (err_last_slot != KEY_NONE) slots.push_back((uint16_t)err_last_slot);
-        replay_trace(slots);
+    void build_trace() { trace_to(err_ref, err_last_slot); }
+
+    // the behaviour that ends at the state with global id g (and then takes the successor with key `last`,
+    // unless KEY_NONE) -> trace; a seeded run's (rmc_init_from) begins at the root the path ends in
+    void trace_to(uint64_t g, uint32_t last) {
+        std::vector<uint64_t> gids;
+        std::vector<uint16_t> slots = path_slots(g, &gids);
+        if (last != KEY_NONE) slots.push_back((uint16_t)last);
+        replay_trace(slots, roots.empty() ? nullptr : roots.data() + gids[0] * (size_t)RECW);
         trace_from_sim = false;
     }
 
-    // the behaviour that takes the successors with these slot keys from Init on -> trace
-    void replay_trace(const std::vector<uint16_t> &slots) {
+    // the behaviour that takes the successors with these slot keys from Init (or the record `from`) on -> trace
+    void replay_trace(const std::vector<uint16_t> &slots, const uint32_t *from = nullptr) {
         trace.clear();
-        std::vector<uint32_t> rec = init_record();
+        std::vector<uint32_t> rec = from ? std::vector<uint32_t>(from, from + RECW) : init_record();
         trace.push_back({unpack(rec.data()), -1, -1, -1});
         for (uint16_t sk : slots) {
             HIPCHK(hipMemcpy(d_one, rec.data(), RECW * 4, hipMemcpyHostToDevice));
@@ -4127,6 +4287,9 @@ struct rmc_ctx {
     // survives until the new one is complete.
     void checkpoint(const char *path_arg) {
         if (!inited || finished) throw Fail(RMC_E_STATE, "checkpoint: between levels of a started, unfinished run");
+        // (the file holds parent references and slot keys, replayed from Init: it has no place for a seeded run's
+        // root records, and a resumed run could not rebuild a counterexample without them)
+        if (!roots.empty()) throw Fail(RMC_E_STATE, "checkpoint: not for a run seeded with rmc_init_from (the file format does not carry the roots)");
         HIPCHK(hipStreamSynchronize(stream));
         if (xstream) HIPCHK(hipStreamSynchronize(xstream));  // (idle between steps: step_single drains it)
         sync_trace();
@@ -4433,6 +4596,8 @@ struct rmc_ctx {
         glevel.clear();
         L_shard = 0;
         replicated = false;
+        roots.clear();  // (a seeded run's: the next rmc_init starts from Init)
+        seed_n = seed_m = 1;
     }
 
     void result(rmc_result *r) const {
@@ -4531,6 +4696,11 @@ int rmc_init(void *ctx, rmc_level_stats *st) {
     return guarded(c, [&] { return c->init(st); });
 }
 
+int rmc_init_from(void *ctx, const int32_t *unpacked, size_t stride_ints, uint64_t n, rmc_level_stats *st) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] { return c->init_from(unpacked, stride_ints, n, st); });
+}
+
 int rmc_step(void *ctx, rmc_level_stats *st) {
     rmc_ctx *c = (rmc_ctx *)ctx;
     return guarded(c, [&] { return c->step(st); });
@@ -4598,7 +4768,8 @@ int rmc_get_coverage(void *ctx, rmc_coverage *out) {
             out->generated[k] = c->cov_total[k];
             out->distinct[k] = c->cov_total[16 + k];
         }
-        out->init_generated = out->init_distinct = 1;
+        out->init_generated = c->seed_n;  // (1:1 unless the run was seeded, rmc_init_from)
+        out->init_distinct = c->seed_m;
         return RMC_OK;
     });
 }
@@ -4753,10 +4924,7 @@ int rmc_violation_trace(void *ctx, uint32_t invariant_bit) {
         if (!c->cont) throw Fail(RMC_E_STATE, "rmc_violation_trace: continuation is off (rmc_set_continue)");
         if (!c->inited) throw Fail(RMC_E_STATE, "rmc_violation_trace before rmc_init");
         if (!c->viol_first_level[invariant_bit]) throw Fail(RMC_E_ARG, "rmc_violation_trace: that invariant has no violation");
-        std::vector<uint16_t> slots = c->path_slots(c->viol_first[invariant_bit], nullptr);
-        if (c->viol_first_slot[invariant_bit] != KEY_NONE) slots.push_back((uint16_t)c->viol_first_slot[invariant_bit]);
-        c->replay_trace(slots);
-        c->trace_from_sim = false;
+        c->trace_to(c->viol_first[invariant_bit], c->viol_first_slot[invariant_bit]);
         return RMC_OK;
     });
 }

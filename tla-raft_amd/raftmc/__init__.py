@@ -209,6 +209,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.rmc_graph_shape.argtypes = [vp, P(_GraphShape)]
         lib.rmc_graph_inv_values.argtypes = [vp, vp, u64]
         lib.rmc_graph_import.argtypes = [vp, u64, u64, vp, vp, vp]
+    if hasattr(lib, "rmc_init_from"):  # (likewise)
+        lib.rmc_init_from.argtypes = [vp, vp, ctypes.c_size_t, u64, P(_LevelStats)]
     _lib = lib
     return lib
 
@@ -652,6 +654,30 @@ class ModelChecker:
     def init(self) -> LevelStats:
         st = _LevelStats()
         self._check(self.lib.rmc_init(self.h, ctypes.byref(st)))
+        self._inited = True
+        self._g_import_n = None
+        ls = self._stats(st)
+        self._levels_list().append(ls)
+        return ls
+
+    def init_from(self, states) -> LevelStats:
+        """Test hook (rmc_init_from), in place of init(): the given states stand where Init's level would --
+        TLC's behaviour with several initial states.  `states`: state dicts, or a 2-D int32 array of unpacked
+        rows.  The first state of each symmetry/VIEW class is kept as a root (global ids in that order)."""
+        import numpy as np
+        if not hasattr(self.lib, "rmc_init_from"):
+            raise RmcError("this librmc.so has no rmc_init_from")
+        if isinstance(states, np.ndarray):
+            arr = np.ascontiguousarray(states, dtype=np.int32)
+        else:
+            rows = [state_to_unpacked(d, self.cfg.n_servers, self.cfg.n_vals) for d in states]
+            arr = np.zeros((len(rows), max([len(r) for r in rows] + [1])), dtype=np.int32)
+            for i, r in enumerate(rows):
+                arr[i, :len(r)] = r
+        if arr.ndim != 2:
+            raise RmcError("RMC_E_ARG: init_from: a 2-D array of unpacked rows")
+        st = _LevelStats()
+        self._check(self.lib.rmc_init_from(self.h, arr.ctypes.data, arr.shape[1], arr.shape[0], ctypes.byref(st)))
         self._inited = True
         self._g_import_n = None
         ls = self._stats(st)
