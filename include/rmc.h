@@ -497,6 +497,84 @@ int rmc_graph_reach_levels(void *ctx, uint64_t *can, uint64_t *cannot, uint32_t 
 int rmc_graph_shape(void *ctx, struct rmc_graph_shape *out);
 int rmc_graph_inv_values(void *ctx, uint16_t *out, uint64_t cap);
 
+/* ---- liveness over the state graph: inevitability (AF P), leads-to (Q ~> P), components ------------------
+ * rmc_graph_reach answers "can P still happen from here"; these answer "must P happen from here", over the
+ * same kept graph, under the same state rules (keep on, something kept or imported: RMC_E_STATE otherwise;
+ * between steps or after the run; imported graphs), spec-independent and off unless called.
+ *
+ * Semantics, in graph terms.  Self-edges are ignored.  A fair behaviour is a maximal path: it is infinite, or it
+ * ends in a state with no non-self edge out (a terminal state).  That is weak fairness on Next over the graph
+ * TLC explores (with the caveat above: each state is its class's first-found member); Raft.tla states no
+ * fairness, so TLC itself has no verdict to compare with.  The target set T is chosen as in rmc_graph_reach
+ * (invariant_bit, value; an evaluation error is in neither set).  `must` is the least fixpoint of
+ *     X = T  u  { s : s has at least one non-self edge out, and every non-self edge out of s ends in X }
+ * and within[g] = 0 for a target, otherwise 1 + the maximum of within over g's non-self successors, 0xFFFFFFFF
+ * for a state outside `must` -- an "avoider": some fair behaviour from it never meets T.
+ *   rmc_graph_eventually         a level-synchronous attractor over the reverse CSR: counters start at the
+ *                                out-degree without self-edges (duplicates counted, and each duplicate entry
+ *                                counts down once), the first frontier is T, every predecessor entry of a frontier
+ *                                state takes one decrement, and the state whose counter goes 1 -> 0 gets within =
+ *                                the round and enters the next frontier (a target never enters a second time).
+ *                                rounds = max_within + 1 (0 with an empty T).  within_out: `states` entries, or
+ *                                NULL.  source_bit >= 0 adds a source set Q (source_bit, source_value, chosen the
+ *                                same way): Q ~> P fails iff source_avoiders > 0.
+ *   rmc_graph_eventually_levels  the last query's must / avoid counts per BFS level, as rmc_graph_reach_levels.
+ *   rmc_graph_avoid_path         the counterexample from an avoider `gid` of the last query.  Every non-terminal
+ *                                avoider has a non-self edge into an avoider; next_avoid[g] is the smallest such
+ *                                dst (one edge-parallel pass after the query).  gids[0] = gid, gids[i + 1] =
+ *                                next_avoid[gids[i]]; the walk ends at a terminal avoider (*loop_at = -1) or at
+ *                                the first state whose next_avoid is already on the path (*loop_at = the index of
+ *                                that successor: a lasso).  Deterministic.  *len states; RMC_E_ARG if gid is no
+ *                                avoider of the last query or cap < *len, RMC_E_STATE without a query (a later
+ *                                rmc_graph_reach, or growth of the graph, ends the query).
+ *   rmc_graph_scc                strongly connected components, self-edges ignored (a state with only a self-edge
+ *                                is a component of its own).  comp_out[g] (`states` entries, or NULL) = the
+ *                                smallest gid of g's component.  Trimming first (Kahn peeling on the out-edges,
+ *                                then on the in-edges), then forward max-gid colour propagation and a backward
+ *                                closure inside each colour, repeated on what is left; an acyclic graph ends in
+ *                                the trimming (trimmed == components == states).  Every host loop is bounded by
+ *                                `states` rounds, every launch by the counts passed to it. */
+typedef struct rmc_live_query {
+    uint32_t invariant_bit;   /* 0..6: the target set P */
+    int32_t value;            /* 1 = TRUE, 0 = FALSE */
+    int32_t source_bit;       /* -1: no source set; 0..6: the source set Q of a leads-to */
+    int32_t source_value;     /* 1 = TRUE, 0 = FALSE */
+} rmc_live_query;
+typedef struct rmc_live_result {
+    uint64_t states, edges, self_edges;
+    uint64_t targets;
+    uint64_t must;            /* targets included (within 0) */
+    uint64_t avoiders;
+    uint64_t avoid_terminal;  /* avoiders with no non-self edge out */
+    uint64_t first_avoid;     /* smallest global id among the avoiders; all ones if there is none */
+    uint64_t sources;         /* with a source set: its states, ... */
+    uint64_t source_avoiders; /* ... those of them that are avoiders, ... */
+    uint64_t first_source_avoid; /* ... and the smallest of these (all ones if none, or no source set) */
+    int32_t first_avoid_level;   /* BFS level (1 = Init's level); 0 if there is none */
+    int32_t first_source_avoid_level;
+    int32_t max_within;       /* the latest state of `must` */
+    int32_t init_within;      /* -1: Init is an avoider */
+    uint32_t rounds;          /* frontier launches of the attractor */
+    uint32_t pad_;
+    double seconds;           /* the attractor and its statistics */
+    double csr_seconds;       /* as in rmc_reach_result */
+} rmc_live_result;
+typedef struct rmc_scc_result {
+    uint64_t components;
+    uint64_t nontrivial;        /* components of two states or more */
+    uint64_t nontrivial_states; /* the states in them */
+    uint64_t largest;           /* states of the largest component */
+    uint64_t trimmed;           /* states removed as components of their own before any colouring */
+    uint32_t rounds;            /* launches whose count the host read */
+    uint32_t pad_;
+    double seconds;
+    double csr_seconds;
+} rmc_scc_result;
+int rmc_graph_eventually(void *ctx, const rmc_live_query *q, rmc_live_result *res, uint32_t *within_out);
+int rmc_graph_eventually_levels(void *ctx, uint64_t *must, uint64_t *avoid, uint32_t cap, uint32_t *n);
+int rmc_graph_avoid_path(void *ctx, uint64_t gid, uint64_t *gids, uint32_t cap, uint32_t *len, int32_t *loop_at);
+int rmc_graph_scc(void *ctx, rmc_scc_result *res, uint32_t *comp_out);
+
 /* Measurement support (bench.py): the random-probe peak of the seen-set layout -- `probes`
  * one-slot reads of 16-B slots at uniformly random indices of a 2^table_log2-slot table,
  * best of 3 timed launches; no model-checking state is touched. */

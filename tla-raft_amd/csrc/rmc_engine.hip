@@ -4863,6 +4863,42 @@ int rmc_graph_inv_values(void *ctx, uint16_t *out, uint64_t cap) {
     });
 }
 
+int rmc_graph_eventually(void *ctx, const rmc_live_query *q, rmc_live_result *res, uint32_t *within_out) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_eventually");
+        c->kept_call([&] { c->kept.eventually(q, res, within_out); });
+        return RMC_OK;
+    });
+}
+
+int rmc_graph_eventually_levels(void *ctx, uint64_t *must, uint64_t *avoid, uint32_t cap, uint32_t *n) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_eventually_levels");
+        c->kept_call([&] { c->kept.eventually_levels(must, avoid, cap, n); });
+        return RMC_OK;
+    });
+}
+
+int rmc_graph_avoid_path(void *ctx, uint64_t gid, uint64_t *gids, uint32_t cap, uint32_t *len, int32_t *loop_at) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_avoid_path");
+        c->kept_call([&] { c->kept.avoid_path(gid, gids, cap, len, loop_at); });
+        return RMC_OK;
+    });
+}
+
+int rmc_graph_scc(void *ctx, rmc_scc_result *res, uint32_t *comp_out) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        kept_ready(c, "rmc_graph_scc");
+        c->kept_call([&] { c->kept.scc(res, comp_out); });
+        return RMC_OK;
+    });
+}
+
 int rmc_graph_import(void *ctx, uint64_t n_states, uint64_t n_edges, const uint32_t *src, const uint32_t *dst,
                      const uint16_t *inv_values) {
     rmc_ctx *c = (rmc_ctx *)ctx;

@@ -55,11 +55,22 @@ struct KeptGraph {
     void reach_levels(uint64_t *can, uint64_t *cannot, uint32_t cap, uint32_t *n);
     void shape(struct rmc_graph_shape *out);
     void inv_values(uint16_t *out, uint64_t cap);
+    // liveness (include/rmc.h "liveness over the state graph")
+    void eventually(const rmc_live_query *q, rmc_live_result *res, uint32_t *within_out);
+    void eventually_levels(uint64_t *must, uint64_t *avoid, uint32_t cap, uint32_t *n);
+    void avoid_path(uint64_t gid, uint64_t *gids, uint32_t cap, uint32_t *len, int32_t *loop_at);
+    void scc(rmc_scc_result *res, uint32_t *comp_out);
 
 private:
-    void grown() { csr = false; have_query = false; }
+    void grown() { csr = false; have_query = false; have_live = false; next_avoid.clear(); }
     void build_csr();
     void analysis_alloc();
     void analysis_free();
+    uint64_t peel(uint32_t *rounds = nullptr);  // Kahn peeling on `work`: the states removed (the counters at 0)
     std::vector<uint64_t> last_can, last_cannot;
+    // the last rmc_graph_eventually: `dist` holds within (a rmc_graph_reach in between takes it back)
+    bool have_live = false;
+    std::vector<uint64_t> last_must, last_avoid;
+    std::vector<uint32_t> next_avoid;  // host copy, filled by the first avoid_path after a query
+    uint32_t *comp = nullptr;          // rmc_graph_scc's labels, allocated by its first call
 };

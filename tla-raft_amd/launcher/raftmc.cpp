@@ -304,7 +304,8 @@ struct DumpSink {
 int usage(const char *msg) {
     std::fprintf(stderr, "raftmc: %s\nusage: raftmc [-deadlock] [-workers N] [-config FILE.cfg] [-device D] "
                          "[-gpus N [-onerank] [-shardmin K]] [-msgcap C] [-seenlog2 K] [-checkpoint MIN] [-metadir DIR] "
-                         "[-recover DIR] [-coverage MIN] [-continue] [-dump [dot[,actionlabels]] FILE] [-canreach NAME[=FALSE]]... FILE.tla\n"
+                         "[-recover DIR] [-coverage MIN] [-continue] [-dump [dot[,actionlabels]] FILE] [-canreach NAME[=FALSE]]... "
+                         "[-eventually NAME[=FALSE]]... [-leadsto Q[=FALSE] P[=FALSE]]... [-scc] FILE.tla\n"
                          "       raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config FILE.cfg] [-device D] "
                          "[-msgcap C] FILE.tla\n"
                          "  -coverage MIN  per-action coverage (distinct:generated) at the end of the search; the interval "
@@ -318,6 +319,12 @@ int usage(const char *msg) {
                          "still reach a state on which invariant NAME is TRUE (=FALSE: is FALSE), and the behaviour to the first "
                          "that cannot; NAME is one of Inv NoSplitVote RaftCanCommt FollowerCanCommit CommitAll NoAllCommit "
                          "ExistLeaderAndCandidate, in the cfg or not; one GPU, not with -simulate or -recover\n"
+                         "  -eventually NAME[=FALSE]  (GPU-specific, repeatable) after the search: from how many distinct states "
+                         "every fair behaviour (a maximal path of the state graph) must reach a state on which NAME is TRUE "
+                         "(=FALSE: is FALSE), how many can avoid it forever, and a counter-example if Init can; the fairness "
+                         "is assumed, not the spec's: the exit code stays the search's\n"
+                         "  -leadsto Q[=FALSE] P[=FALSE]  (likewise) Q ~> P: a counter-example if a state where Q holds can avoid P\n"
+                         "  -scc  (likewise) the strongly connected components of the state graph, self-loops ignored\n"
                          "  -simulate  random behaviours instead of the breadth-first search; num=N of them (default "
                          "1000000; TLC's default is unbounded)\n"
                          "  -depth D   states per behaviour at most (default 100, as TLC)\n"
@@ -521,6 +528,26 @@ int main(int argc, char **argv) {
     std::string dump_file, dump_bad;
     std::vector<std::pair<int, int>> canreach;  // -canreach NAME[=FALSE]: (invariant bit, value)
     std::string canreach_bad;
+    // -eventually NAME[=FALSE] / -leadsto Q[=FALSE] P[=FALSE]: target (bit, value), source (bit, value) or bit -1; -scc
+    struct LiveQ { int bit, value, sbit, svalue; };
+    std::vector<LiveQ> liveq;
+    std::string live_bad, live_flag;  // the first argument that names no invariant, and its flag
+    bool scc = false;
+    auto inv_arg = [&](const std::string &v, int *bit, int *value) {  // NAME[=TRUE|=FALSE]
+        *value = 1;
+        *bit = -1;
+        const size_t eq = v.find('=');
+        const std::string name = v.substr(0, eq);
+        if (eq != std::string::npos) {
+            const std::string t = v.substr(eq + 1);
+            if (t == "FALSE") *value = 0;
+            else if (t != "TRUE") return false;
+        }
+        if (name == "LeaderHasAllCommittedEntries") *bit = 0;
+        for (int b = 0; b < 7 && *bit < 0; b++)
+            if (name == kInvNames[b]) *bit = b;
+        return *bit >= 0;
+    };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *f) -> const char * {
@@ -583,6 +610,23 @@ int main(int argc, char **argv) {
             if (bit < 0 && canreach_bad.empty()) canreach_bad = v;
             canreach.push_back({bit, value});
         }
+        else if (a == "-eventually") {
+            const std::string v = need("-eventually");
+            LiveQ q{-1, 1, -1, 1};
+            if (!inv_arg(v, &q.bit, &q.value) && live_bad.empty()) { live_bad = v; live_flag = a; }
+            liveq.push_back(q);
+        }
+        else if (a == "-leadsto") {
+            auto is_tla = [](const char *s) { const size_t k = std::strlen(s); return k > 4 && std::strcmp(s + k - 4, ".tla") == 0; };
+            if (i + 2 >= argc || argv[i + 1][0] == '-' || argv[i + 2][0] == '-' || is_tla(argv[i + 1]) || is_tla(argv[i + 2]))
+                return usage("-leadsto takes two arguments: Q[=FALSE] P[=FALSE] (from a state where Q holds, P must follow)");
+            const std::string qs = argv[++i], ps = argv[++i];
+            LiveQ q{-1, 1, -1, 1};
+            if (!inv_arg(qs, &q.sbit, &q.svalue) && live_bad.empty()) { live_bad = qs; live_flag = a; }
+            if (!inv_arg(ps, &q.bit, &q.value) && live_bad.empty()) { live_bad = ps; live_flag = a; }
+            liveq.push_back(q);
+        }
+        else if (a == "-scc") scc = true;
         else if (a == "-depth") sim_depth = std::atoll(need("-depth"));
         else if (a == "-seed") { sim_seed = (unsigned long long)std::strtoll(need("-seed"), nullptr, 10); seed_given = true; }
         else if (a == "-metadir") metadir = need("-metadir");
@@ -620,6 +664,16 @@ int main(int argc, char **argv) {
         if (!recover_dir.empty()) return usage("-canreach cannot be combined with -recover (checkpoints do not carry the state graph)");
         if (gpus > 1 || onerank) return usage("-canreach runs on one GPU (no -gpus)");
     }
+    if (!liveq.empty() || scc) {  // refused before anything touches a device
+        const std::string f = !live_flag.empty() ? live_flag : !liveq.empty() ? (liveq[0].sbit >= 0 ? "-leadsto" : "-eventually") : "-scc";
+        if (!live_bad.empty())
+            return usage((live_flag + " " + live_bad + ": NAME[=TRUE|=FALSE] with NAME one of Inv, NoSplitVote, RaftCanCommt, "
+                          "FollowerCanCommit, CommitAll, NoAllCommit, ExistLeaderAndCandidate").c_str());
+        if (simulate) return usage((f + " cannot be combined with -simulate").c_str());
+        if (!recover_dir.empty()) return usage((f + " cannot be combined with -recover (checkpoints do not carry the state graph)").c_str());
+        if (gpus > 1 || onerank) return usage((f + " runs on one GPU (no -gpus)").c_str());
+    }
+    const bool keep_graph = !canreach.empty() || !liveq.empty() || scc;  // the analyses after the search need the graph
     if (simulate) {  // refused before anything touches a device
         if (sim_bad) return usage("-simulate takes num=N with N >= 1");
         if (sim_depth < 1 || sim_depth > 0x7FFFFFFFll) return usage("-depth must be at least 1");
@@ -699,26 +753,32 @@ int main(int argc, char **argv) {
         }
         return out;
     };
+    // "<Action line .. of module M>" of the step (a, s) taken from the state `from` (unpacked: vf, ct, role)
+    auto action_title = [&](int32_t a, int32_t s, const int32_t *from, const rmc_config &cfg) -> std::string {
+        static std::vector<std::string> names;
+        static std::vector<Loc> locs;
+        if (names.empty()) {
+            names.assign(kActionNames, kActionNames + 13);
+            names.insert(names.end(), kBfNames, kBfNames + 3);  // 13..15
+            locs = action_locations(tla, names);
+        }
+        const int an = (a == 12 && s >= 0 && s < cfg.n_servers) ? 13 + (from ? from[2 * cfg.n_servers + s] : 0) : a;  // role: 0 F, 1 C, 2 L
+        const Loc &L = locs[an];
+        char buf[256];
+        if (L.l0)
+            std::snprintf(buf, sizeof buf, "<%s line %d, col %d to line %d, col %d of module %s>", names[an].c_str(), L.l0, L.c0,
+                          L.l1, L.c1, pm.module.c_str());
+        else
+            std::snprintf(buf, sizeof buf, "<%s(%s)>", names[an].c_str(), pm.servers[s].c_str());
+        return buf;
+    };
     auto print_behavior = [&](const std::vector<Step> &steps, const rmc_config &cfg) {
-        std::vector<std::string> names(kActionNames, kActionNames + 13);
-        names.insert(names.end(), kBfNames, kBfNames + 3);  // 13..15
-        std::vector<Loc> locs = action_locations(tla, names);
         Printer pr{pm, cfg.n_servers, cfg.n_vals};
-        std::vector<int32_t> prev_role(cfg.n_servers, 0);
         for (uint32_t i = 0; i < (uint32_t)steps.size(); i++) {
             const std::vector<int32_t> &buf = steps[i].buf;
             const int32_t a = steps[i].a, s = steps[i].s;
             if (a < 0) std::printf("State %u: <Initial predicate>\n", i + 1);
-            else {
-                const int an = (a == 12 && s >= 0 && s < cfg.n_servers) ? 13 + prev_role[s] : a;  // role: 0 F, 1 C, 2 L
-                const Loc &L = locs[an];
-                if (L.l0)
-                    std::printf("State %u: <%s line %d, col %d to line %d, col %d of module %s>\n", i + 1,
-                                names[an].c_str(), L.l0, L.c0, L.l1, L.c1, pm.module.c_str());
-                else
-                    std::printf("State %u: <%s(%s)>\n", i + 1, names[an].c_str(), pm.servers[s].c_str());
-            }
-            for (int q = 0; q < cfg.n_servers; q++) prev_role[q] = buf[2 * cfg.n_servers + q];  // unpacked: vf, ct, role
+            else std::printf("State %u: %s\n", i + 1, action_title(a, s, i ? steps[i - 1].buf.data() : nullptr, cfg).c_str());
             std::printf("%s\n", pr.state(buf.data()).c_str());
         }
     };
@@ -811,7 +871,7 @@ int main(int argc, char **argv) {
         rmc_destroy(ctx);
         return 75;
     }
-    if (!canreach.empty() && rmc_set_graph_keep(ctx, 1) < 0) {
+    if (keep_graph && rmc_set_graph_keep(ctx, 1) < 0) {
         std::printf("Error: %s\n", rmc_last_error(ctx));
         rmc_destroy(ctx);
         return 75;
@@ -889,7 +949,7 @@ int main(int argc, char **argv) {
         const auto now = std::chrono::steady_clock::now();
         // (-dump runs a level per call where the plain run's first call covers a device-driven batch of them: its
         // first report waits for the interval or the closing one, so both runs print the same lines)
-        if ((!reported && !dump && canreach.empty()) || std::chrono::duration<double>(now - last_progress).count() >= progress_s) {
+        if ((!reported && !dump && !keep_graph) ||std::chrono::duration<double>(now - last_progress).count() >= progress_s) {
             progress(last);
             reported = true;
             printed_level = last.level;
@@ -981,6 +1041,98 @@ int main(int argc, char **argv) {
         if (rmc_graph_shape(ctx, &gsh) < 0) std::printf("Error: no graph shape: %s\n", rmc_last_error(ctx));
         else if (!gsh.cyclic_states) std::printf("The state graph has no cycle other than self-loops.\n");
         else std::printf("The state graph has %llu states on or leading to cycles.\n", (unsigned long long)gsh.cyclic_states);
+    }
+    // -eventually / -leadsto: one line per query; when the property fails, the behaviour to the first (source) avoider
+    // and the avoid walk from it.  Every state printed is its class's stored member (path_steps replays it from Init);
+    // a step's action is that of the first successor of the member with the next member's fingerprint.
+    for (const LiveQ &lq : liveq) {
+        rmc_live_query q{(uint32_t)lq.bit, lq.value, lq.sbit, lq.svalue};
+        rmc_live_result lr;
+        const std::string what = std::string(kInvNames[lq.bit]) + " = " + (lq.value ? "TRUE" : "FALSE");
+        if (rmc_graph_eventually(ctx, &q, &lr, nullptr) < 0) {
+            std::printf("Error: no inevitability of %s: %s\n", kInvNames[lq.bit], rmc_last_error(ctx));
+            continue;
+        }
+        const bool leads = lq.sbit >= 0;
+        const std::string init_w = lr.init_within < 0 ? std::string("Init can avoid it") : "Init: " + std::to_string(lr.init_within) + " steps";
+        if (leads)
+            std::printf("Leads-to %s = %s ~> %s: %llu of %llu distinct states satisfy the first, %llu of them can avoid the second "
+                        "forever%s; ", kInvNames[lq.sbit], lq.svalue ? "TRUE" : "FALSE", what.c_str(), (unsigned long long)lr.sources,
+                        (unsigned long long)lr.states,
+                        (unsigned long long)lr.source_avoiders,
+                        lr.source_avoiders ? (" (first at depth " + std::to_string(lr.first_source_avoid_level) + ")").c_str() : "");
+        else
+            std::printf("Inevitability of %s: ", what.c_str());
+        std::printf("%llu of %llu distinct states satisfy it, %llu must reach one (latest: %d steps, %s), %llu can avoid it forever",
+                    (unsigned long long)lr.targets, (unsigned long long)lr.states, (unsigned long long)lr.must, lr.max_within,
+                    init_w.c_str(), (unsigned long long)lr.avoiders);
+        if (lr.avoiders)
+            std::printf(" (first at depth %d; %llu of them end where no step leads out).\n", lr.first_avoid_level,
+                        (unsigned long long)lr.avoid_terminal);
+        else std::printf(".\n");
+        const bool fails = leads ? lr.source_avoiders > 0 : lr.init_within < 0;
+        if (!fails) continue;
+        std::printf("Error: Temporal properties were violated.\n");
+        std::printf("Error: The following behavior constitutes a counter-example:\n");
+        const uint64_t from = leads ? lr.first_source_avoid : lr.first_avoid;  // (-eventually: Init, gid 0)
+        std::vector<uint64_t> walk(4096);
+        uint32_t wl = 0;
+        int32_t loop_at = -1;
+        int wrc = rmc_graph_avoid_path(ctx, from, walk.data(), (uint32_t)walk.size(), &wl, &loop_at);
+        if (wrc < 0 && wl > walk.size()) {
+            walk.resize(wl);
+            wrc = rmc_graph_avoid_path(ctx, from, walk.data(), (uint32_t)walk.size(), &wl, &loop_at);
+        }
+        std::vector<Step> steps = wrc < 0 ? std::vector<Step>() : path_steps(ctx, cfg, from);
+        if (steps.empty()) {
+            std::printf("Error: no behaviour from state %llu: %s\n", (unsigned long long)from, rmc_last_error(ctx));
+            continue;
+        }
+        const size_t stem = steps.size() - 1;  // the walk's state i is state stem + i of the behaviour
+        const size_t stride = RMC_UNPACKED_INTS(5, 3, 256);
+        const uint32_t cap = 1024;
+        std::vector<int32_t> succ(cap * stride);
+        std::vector<uint32_t> sk(cap);
+        std::vector<uint64_t> sfp(2 * (size_t)cap);
+        // the key of the first successor of `a` whose fingerprint is b's; false if there is none
+        auto step_key = [&](const std::vector<int32_t> &a, const std::vector<int32_t> &b, uint32_t *key) {
+            uint32_t cnt = 0;
+            uint64_t fp[2];
+            if (rmc_fingerprint(ctx, b.data(), fp) != RMC_OK) return false;
+            if (rmc_successors(ctx, a.data(), succ.data(), stride, cap, sk.data(), sfp.data(), &cnt) != RMC_OK) return false;
+            for (uint32_t j = 0; j < cnt; j++)
+                if (sfp[2 * j] == fp[0] && sfp[2 * j + 1] == fp[1]) {
+                    *key = sk[j];
+                    return true;
+                }
+            return false;
+        };
+        bool ok = true;
+        for (uint32_t i = 1; i < wl && ok; i++) {
+            std::vector<Step> member = path_steps(ctx, cfg, walk[i]);
+            uint32_t key = 0;
+            ok = !member.empty() && step_key(steps.back().buf, member.back().buf, &key);
+            if (ok) steps.push_back(Step{member.back().buf, (int32_t)((key >> 16) & 0xFF), (int32_t)(key >> 24), (int32_t)(key & 0xFFFF)});
+        }
+        uint32_t back_key = 0;
+        if (ok && loop_at >= 0) ok = step_key(steps.back().buf, steps[stem + loop_at].buf, &back_key);
+        if (!ok) {
+            std::printf("Error: the behaviour from state %llu does not resolve: %s\n", (unsigned long long)from, rmc_last_error(ctx));
+            continue;
+        }
+        print_behavior(steps, cfg);
+        if (loop_at < 0) std::printf("State %zu: Stuttering\n", steps.size() + 1);
+        else
+            std::printf("Back to state %zu: %s\n", stem + loop_at + 1,
+                        action_title((int32_t)((back_key >> 16) & 0xFF), (int32_t)(back_key >> 24), steps.back().buf.data(), cfg).c_str());
+    }
+    if (scc) {
+        rmc_scc_result sr;
+        if (rmc_graph_scc(ctx, &sr, nullptr) < 0) std::printf("Error: no components: %s\n", rmc_last_error(ctx));
+        else
+            std::printf("The state graph has %llu strongly connected components: %llu of more than one state (%llu states, the "
+                        "largest %llu).\n", (unsigned long long)sr.components, (unsigned long long)sr.nontrivial,
+                        (unsigned long long)sr.nontrivial_states, (unsigned long long)sr.largest);
     }
     rmc_coverage cov;
     const int cov_rc = coverage && cfg.rank == 0 ? rmc_get_coverage(ctx, &cov) : RMC_OK;

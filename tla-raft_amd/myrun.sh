@@ -5,5 +5,8 @@
 # GPU-specific flags go through with the rest, next to -gpus N:
 #   -canreach NAME | -canreach NAME=FALSE   (repeatable) after the verdict, how many distinct states can still reach
 #   a state on which invariant NAME is TRUE (FALSE), and the behaviour to the first one that cannot
+#   -eventually NAME[=FALSE] | -leadsto Q[=FALSE] P[=FALSE]   (repeatable) from how many states NAME must follow on every
+#   fair behaviour, how many can avoid it forever, and a counter-example (a lasso or a dead end) when the property fails
+#   -scc   the strongly connected components of the state graph
 DIR=$(cd "$(dirname "$0")" && pwd)
 "$DIR/build/raftmc" -deadlock -workers 4 -config Raft.cfg Raft.tla $@ 2>&1 | tee raft.log

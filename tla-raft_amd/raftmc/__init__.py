@@ -144,6 +144,27 @@ class _GraphShape(ctypes.Structure):
                 ("in_hist", ctypes.c_uint64 * 64), ("out_hist", ctypes.c_uint64 * 64)]
 
 
+class _LiveQuery(ctypes.Structure):
+    _fields_ = [("invariant_bit", ctypes.c_uint32), ("value", ctypes.c_int32), ("source_bit", ctypes.c_int32),
+                ("source_value", ctypes.c_int32)]
+
+
+class _LiveResult(ctypes.Structure):
+    _fields_ = [("states", ctypes.c_uint64), ("edges", ctypes.c_uint64), ("self_edges", ctypes.c_uint64),
+                ("targets", ctypes.c_uint64), ("must", ctypes.c_uint64), ("avoiders", ctypes.c_uint64),
+                ("avoid_terminal", ctypes.c_uint64), ("first_avoid", ctypes.c_uint64), ("sources", ctypes.c_uint64),
+                ("source_avoiders", ctypes.c_uint64), ("first_source_avoid", ctypes.c_uint64),
+                ("first_avoid_level", ctypes.c_int32), ("first_source_avoid_level", ctypes.c_int32),
+                ("max_within", ctypes.c_int32), ("init_within", ctypes.c_int32), ("rounds", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32), ("seconds", ctypes.c_double), ("csr_seconds", ctypes.c_double)]
+
+
+class _SccResult(ctypes.Structure):
+    _fields_ = [("components", ctypes.c_uint64), ("nontrivial", ctypes.c_uint64), ("nontrivial_states", ctypes.c_uint64),
+                ("largest", ctypes.c_uint64), ("trimmed", ctypes.c_uint64), ("rounds", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32), ("seconds", ctypes.c_double), ("csr_seconds", ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -209,6 +230,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.rmc_graph_shape.argtypes = [vp, P(_GraphShape)]
         lib.rmc_graph_inv_values.argtypes = [vp, vp, u64]
         lib.rmc_graph_import.argtypes = [vp, u64, u64, vp, vp, vp]
+    if hasattr(lib, "rmc_graph_eventually"):  # (likewise)
+        lib.rmc_graph_eventually.argtypes = [vp, P(_LiveQuery), P(_LiveResult), vp]
+        lib.rmc_graph_eventually_levels.argtypes = [vp, P(u64), P(u64), u32, P(u32)]
+        lib.rmc_graph_avoid_path.argtypes = [vp, u64, P(u64), u32, P(u32), P(i32)]
+        lib.rmc_graph_scc.argtypes = [vp, P(_SccResult), vp]
     if hasattr(lib, "rmc_init_from"):  # (likewise)
         lib.rmc_init_from.argtypes = [vp, vp, ctypes.c_size_t, u64, P(_LevelStats)]
     _lib = lib
@@ -587,6 +613,51 @@ class ReachResult:
 
 
 @dataclass
+class LiveResult:
+    """rmc_graph_eventually's result (include/rmc.h rmc_live_result); first_avoid / first_avoid_level / init_within
+    are None where the library reports none, the source fields None without a source set; within: numpy u32 per state
+    (0xFFFFFFFF = avoider) with want_within."""
+    invariant: str
+    value: bool
+    source: Optional[str]
+    source_value: Optional[bool]
+    states: int
+    edges: int
+    self_edges: int
+    targets: int
+    must: int
+    avoiders: int
+    avoid_terminal: int
+    first_avoid: Optional[int]
+    first_avoid_level: Optional[int]
+    max_within: int
+    init_within: Optional[int]
+    sources: Optional[int]
+    source_avoiders: Optional[int]
+    first_source_avoid: Optional[int]
+    first_source_avoid_level: Optional[int]
+    rounds: int
+    seconds: float
+    csr_seconds: float
+    within: object = None
+
+
+@dataclass
+class SccResult:
+    """rmc_graph_scc's result (include/rmc.h rmc_scc_result); comp: numpy u32 per state, the smallest gid of its
+    component, with want_comp."""
+    components: int
+    nontrivial: int
+    nontrivial_states: int
+    largest: int
+    trimmed: int
+    rounds: int
+    seconds: float
+    csr_seconds: float
+    comp: object = None
+
+
+@dataclass
 class SimResult:
     """ModelChecker.simulate: the accounted walks (0..err_walk on an error, all of them otherwise)."""
     status: str
@@ -957,6 +1028,63 @@ class ModelChecker:
         self._check(self.lib.rmc_graph_import(self.h, n_states, s.size, s.ctypes.data if s.size else None,
                                               d.ctypes.data if d.size else None, v.ctypes.data))
         self._g_import_n = n_states
+
+    # ---- liveness over the kept state graph (include/rmc.h rmc_graph_eventually) ----
+    def graph_eventually(self, invariant: str, value: bool = True, source: Optional[str] = None,
+                         source_value: bool = True, want_within: bool = False) -> LiveResult:
+        """Which states must reach a state on which `invariant` is `value` on every fair behaviour (a maximal path,
+        self-edges ignored), and which can avoid it forever: an attractor on the device over the kept graph.  With
+        `source`, the leads-to `source = source_value ~> invariant = value`: it fails iff source_avoiders > 0."""
+        import numpy as np
+        if not hasattr(self.lib, "rmc_graph_eventually"):
+            raise RmcError("this librmc.so has no liveness queries (rmc_graph_eventually): rebuild it")
+        q = _LiveQuery(self._inv_bit(invariant), 1 if value else 0, -1 if source is None else self._inv_bit(source),
+                       1 if source_value else 0)
+        r = _LiveResult()
+        within = np.empty(self._kept_states(), dtype=np.uint32) if want_within else None
+        self._check(self.lib.rmc_graph_eventually(self.h, ctypes.byref(q), ctypes.byref(r),
+                                                  within.ctypes.data if within is not None else None))
+        ones = 0xFFFFFFFFFFFFFFFF
+        none, snone, src = r.first_avoid == ones, r.first_source_avoid == ones, source is not None
+        return LiveResult(invariant, bool(value), source, bool(source_value) if src else None, r.states, r.edges,
+                          r.self_edges, r.targets, r.must, r.avoiders, r.avoid_terminal,
+                          None if none else r.first_avoid, None if none else r.first_avoid_level, r.max_within,
+                          None if r.init_within < 0 else r.init_within, r.sources if src else None,
+                          r.source_avoiders if src else None, None if snone or not src else r.first_source_avoid,
+                          None if snone or not src else r.first_source_avoid_level, r.rounds, r.seconds, r.csr_seconds,
+                          within)
+
+    def graph_eventually_levels(self) -> List[Tuple[int, int]]:
+        """The last graph_eventually()'s (must, avoid) per BFS level ([0]: Init's level)."""
+        cap = 4096
+        must, avoid, n = (ctypes.c_uint64 * cap)(), (ctypes.c_uint64 * cap)(), ctypes.c_uint32()
+        self._check(self.lib.rmc_graph_eventually_levels(self.h, must, avoid, cap, ctypes.byref(n)))
+        return list(zip(must[:n.value], avoid[:n.value]))
+
+    def graph_avoid_path(self, gid: int) -> Tuple[List[int], Optional[int]]:
+        """The counterexample from an avoider of the last graph_eventually(): (gids, loop_at) -- gids[0] = gid, each
+        next one the smallest successor that is an avoider; loop_at = the index on the path the last state steps back
+        to (a lasso), or None when the walk ends in a state with no step out."""
+        cap = 1024
+        while True:
+            gids, n, at = (ctypes.c_uint64 * cap)(), ctypes.c_uint32(), ctypes.c_int32()
+            rc = self.lib.rmc_graph_avoid_path(self.h, gid, gids, cap, ctypes.byref(n), ctypes.byref(at))
+            if rc < 0 and n.value > cap:  # (the walk is longer than the buffer: its length came back)
+                cap = n.value
+                continue
+            self._check(rc)
+            return list(gids[:n.value]), None if at.value < 0 else at.value
+
+    def graph_scc(self, want_comp: bool = False) -> SccResult:
+        """The strongly connected components of the kept graph, self-edges ignored (include/rmc.h rmc_graph_scc)."""
+        import numpy as np
+        if not hasattr(self.lib, "rmc_graph_scc"):
+            raise RmcError("this librmc.so has no liveness queries (rmc_graph_scc): rebuild it")
+        r = _SccResult()
+        comp = np.empty(self._kept_states(), dtype=np.uint32) if want_comp else None
+        self._check(self.lib.rmc_graph_scc(self.h, ctypes.byref(r), comp.ctypes.data if comp is not None else None))
+        return SccResult(r.components, r.nontrivial, r.nontrivial_states, r.largest, r.trimmed, r.rounds, r.seconds,
+                         r.csr_seconds, comp)
 
     def trace(self) -> List[Tuple[Optional[Tuple[int, int, int]], dict]]:
         n = ctypes.c_uint32()
