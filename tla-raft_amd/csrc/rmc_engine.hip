@@ -930,6 +930,7 @@ struct rmc_ctx {
         P.seeded = cfg.spec_variant == RMC_SPEC_SEEDED;
         P.quirks = (cfg.spec_variant == RMC_SPEC_SPLIT_BRAIN ? 1u : 0u) | (cfg.spec_variant == RMC_SPEC_COMMIT_PAST_LOG ? 2u : 0u);
         P.check_deadlock = cfg.check_deadlock;
+        P.prefilter = item_prefilter;
         P.inv_mask = cfg.invariants;
         P.inv_order = inv_order;
         P.t.info = d_info;
@@ -995,6 +996,14 @@ struct rmc_ctx {
     const uint32_t probe_dedup = probe_dedup_entries();
     const uint32_t probe_run = (uint32_t)env_int("RMC_PROBE_RUN", 0, 0, 64);
     const int probe_log = env_int("RMC_PROBE_DEDUP_LOG", 0, 0, 1);
+
+    // ---- the split expansion's item pre-filter (k_expand_items) ------------------------------------
+    // RMC_ITEM_PREFILTER (read once): bit 0 = messages whose HandleAppendResp guard fails and slots whose
+    // guards fail without a lookup are never listed as items; 0 = every message some action may receive and
+    // every slot of the role's range is an item.  Bit 1 was the reply's membership in msgs for ResponseVote /
+    // FollowerAccept / RejectEntry, measured and dropped: it is ignored.  Each setting is
+    // an instantiation of the kernel (Launch::split); the fused (device-loop) expansion lists as with 0.
+    const uint32_t item_prefilter = (uint32_t)env_int("RMC_ITEM_PREFILTER", RMC_ITEM_PREFILTER_DEFAULT, 0, 3) & 1u;
 
     // ---- grids of a single-GPU split chunk's expansion and items commit -------------------------------
     // Both kernels' blocks stride over batches of 64 parents, so the grid is a whole number of resident

@@ -87,6 +87,7 @@ constexpr int SUM_SELF = 17;     // ... and the self-loops set apart (KParams::h
 constexpr int SUM_HFP = 18;      // ... and a split chunk's successors to fingerprint (its expansion counts them; the
                                  // election of k_hash_probe takes a table of twice as many slots; zeroed with SUM_SELF)
 constexpr uint32_t PD_ENTRIES = 512;  // k_hash_probe: entries of 16 B in a wave's table of recent fingerprints
+constexpr int RMC_ITEM_PREFILTER_DEFAULT = 1;  // KParams::prefilter where RMC_ITEM_PREFILTER is unset
 constexpr int PROBE_RUN = 2;     // ... and the groups of 64 parents a wave takes in a row (KParams::prun)
 constexpr int SUM_OCNT = 20;    // ... a sharded round's successors per owner shard (u32[64] over sum[20 .. 52): zeroed
                                  // with SUM_INS .. SUM_HFP by one memset per round)
@@ -174,6 +175,9 @@ struct KParams {
     // parents a wave takes in a row, over which its table carries on (0: the launcher's choice, which it
     // passes to the kernel here)
     uint32_t pdedup, prun;
+    // k_expand_items of a split chunk: 1 = items whose guards fail without a lookup are never listed
+    // (RMC_ITEM_PREFILTER; the launcher picks the kernel's instantiation by it)
+    uint32_t prefilter;
     // test variants: bit 0 RaftSplitBrain (BecomeLeader's quorum 1), bit 1 RaftCommitPastLog
     // (FollowerAcceptEntry's newCommitIndex without Min(., Len(newLog)))
     uint32_t quirks;

@@ -34,10 +34,14 @@
 #ifdef RMC_PHASE_PROF
 // (slots 0-7 k_expand, 8-15 k_commit: PHASE_BASE)
 __device__ unsigned long long g_phase[16];
-#define PHASE_DECL unsigned long long _acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long _tp = clock64();
+#define PHASE_DECL unsigned long long _acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, _cn[3] = {0, 0, 0}; (void)_cn; long long _tp = clock64();
 #define PHASE(k) do { const long long _t = clock64(); _acc[k] += (unsigned long long)(_t - _tp); _tp = _t; } while (0)
 #define PHASE_FLUSH_AT(b) do { if (threadIdx.x == 0) for (int _k = 0; _k < 8; _k++) atomicAdd(&g_phase[(b) + _k], _acc[_k]); } while (0)
-#define PHASE_FLUSH PHASE_FLUSH_AT(0)
+// counts of k_expand_items, thread 0 of each block: 0 batches, 1 item rounds, 2 items listed -- flushed with the
+// clocks into the slots k_commit leaves free (11, 14, 15: the commits time PHASE(0), (1), (2), (4) and (5) only, and
+// a PHASE(3), (6) or (7) added there would be added into these counts -- widen g_phase first)
+#define PHASE_COUNT(i, n) do { _cn[i] += (unsigned long long)(n); } while (0)
+#define PHASE_FLUSH do { PHASE_FLUSH_AT(0); if (threadIdx.x == 0) { atomicAdd(&g_phase[11], _cn[0]); atomicAdd(&g_phase[14], _cn[1]); atomicAdd(&g_phase[15], _cn[2]); } } while (0)
 extern "C" int rmc_debug_phases(unsigned long long *out, int reset) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
     if (reset) {
@@ -51,6 +55,7 @@ extern "C" int rmc_debug_phases(unsigned long long *out, int reset) {
 #define PHASE(k) do {} while (0)
 #define PHASE_FLUSH do {} while (0)
 #define PHASE_FLUSH_AT(b) do {} while (0)
+#define PHASE_COUNT(i, n) do {} while (0)
 #endif
 
 #ifndef RMC_N3_WAVES  // n = 3 expansion (and commit): waves per SIMD the register budget is cut for
@@ -1874,6 +1879,17 @@ __device__ __forceinline__ void row_stage(const RowSucc<NADD> &o, uint32_t nm, i
     if (sw4 > 2) dst[2] = make_uint4(a[2] | (a[3] << 16), 0u, 0u, 0u);
 }
 
+// ---- the items' guards that need no lookup: one definition each, called by the evaluation (item_msg /
+// item_slot) and by the item pre-filter of k_expand_items, which drops an item before it takes a lane ----
+// HandleAppendResp's guard (tla:374-396) for the AppendResp m at the leader s: rows of s
+template <int N>
+__device__ __forceinline__ bool har_guard(uint32_t pend, uint32_t mirow, uint32_t nirow, uint32_t s, uint32_t m) {
+    const uint32_t src = mi_src(m), pli = mi_x1(m);
+    if (!((pend >> (s * N + src)) & 1u)) return false;
+    const uint32_t mi = nib(mirow, src), ni = nib(nirow, src);
+    return mi_x2(m) ? mi < pli : (pli + 1 == ni && pli > mi);
+}
+
 // The message item k (info word m) of a parent whose nibble core is pc (LDS) -> at most one successor
 // o (and with BFV the BecomeFollower one, ob).  The same guards and updates as eval_msg, on the row of
 // s = m.dst; pid is the id of the one message the action may send (looked up before any branch).
@@ -1964,18 +1980,13 @@ __device__ __forceinline__ void item_msg(const KParams &P, const uint32_t *pc, c
         return;
     }
     if (typ == ARESP && role == LEA) {  // HandleAppendResp tla:374-396
-        const uint32_t pb = s * N + src;
-        if (!((pend >> pb) & 1u)) return;
-        const uint32_t pli = mi_x1(m);
-        const uint32_t mi = nib(mirow, src), ni = nib(nirow, src);
+        if (!har_guard<N>(pend, mirow, nirow, s, m)) return;
+        const uint32_t pb = s * N + src, pli = mi_x1(m);
         uint32_t nmi = mirow, nni = nirow;
         if (mi_x2(m)) {
-            if (!(mi < pli)) return;
             nmi = setnib(mirow, src, pli);
             nni = setnib(nirow, src, pli + 1);
         } else {
-            if (!(pli + 1 == ni)) return;
-            if (!(pli > mi)) return;
             nni = setnib(nirow, src, pli);
         }
         o.mirow = nmi;
@@ -2000,6 +2011,27 @@ __device__ __forceinline__ uint32_t item_msg_nat(const KParams &P, const uint32_
     return match ? nat_aresp(P.d, s, src, mt, pli + ent, 1) : nat_aresp(P.d, s, src, mt, pli, 0);
 }
 
+// The guards of the non-message slot t of server s that need no lookup: all of them but LeaderAppendEntry's
+// `m \notin msgs` (tla:262; BecomeCandidate's VoteReqs are added or not, never a guard).  vp: VoteResps to s in
+// its term.  Called by item_slot and, a lane per (parent, server), by the pre-filter's slot masks.
+template <int N, int V>
+__device__ __forceinline__ bool slot_guard(const KParams &P, const uint32_t *pc, uint32_t vp, uint32_t s, uint32_t t) {
+    using Lo = Layout<N, V>;
+    const uint32_t role = nib(pc[Lo::W_ROLE], s), misc = pc[Lo::W_MISC];
+    if (t == 0) return (int)(misc & 15u) < P.E && (role == FOL || role == CAN);  // BecomeCandidate tla:107-130
+    if (t == 1)  // BecomeLeader tla:157-173 (RaftSplitBrain: quorum 1)
+        return role == CAN && vp + 1 >= ((P.quirks & 1u) ? 1u : (uint32_t)(N / 2 + 1));
+    if (role != LEA) return false;
+    if (t < 2 + (uint32_t)V) return !((misc >> (8 + (t - 2))) & 1u);  // ClientReq tla:233-240: valSent[v] = None
+    if (t < 2 + (uint32_t)V + (N - 1)) {  // LeaderAppendEntry tla:242-269
+        const uint32_t q = t - 2 - V, dst = q < s ? q : q + 1;
+        return nib(pc[Lo::W_NI + s], dst) <= nib(pc[Lo::W_LL], s) + 1 && !((pc[Lo::W_PEND] >> (s * N + dst)) & 1u);
+    }
+    if (t == 2 + (uint32_t)V + (N - 1))  // LeaderCanCommit tla:398-407
+        return median_row<N>(pc[Lo::W_MI + s], P.seeded ? (uint32_t)N : (uint32_t)(N / 2 + 1)) > nib(pc[Lo::W_CI], s);
+    return (int)((misc >> 4) & 15u) < P.R;  // Restart tla:409-414
+}
+
 // The non-message slot t of server s (eval_slot's slots: 0 BecomeCandidate, 1 BecomeLeader, 2 .. 1 + V
 // ClientReq, then LeaderAppendEntry per peer, LeaderCanCommit, Restart) -> at most one successor.
 template <int N, int V, int MR>
@@ -2018,9 +2050,9 @@ __device__ __forceinline__ void item_slot(const KParams &P, const uint32_t *pc, 
     for (int a = 0; a < S::NADD; a++) o.add[a] = 0;
     o.lw = lw; o.mirow = mirow; o.nirow = nirow; o.pend = pend; o.misc = misc;
     o.w0 = row_w0(vf, ct, role, ci, ll, s);
+    if (!slot_guard<N, V>(P, pc, vp, s, t)) return;  // (every guard of the slot but LeaderAppendEntry's m \notin msgs)
     if (t == 0) {  // BecomeCandidate tla:107-130
         const uint32_t ec = misc & 15u;
-        if (!((int)ec < P.E) || !(role == FOL || role == CAN)) return;
         const uint32_t term = ct + 1, llt = lw_term(lw, ll);
         uint32_t sid[N - 1];  // the VoteReqs to the N - 1 peers, looked up together
 #pragma unroll
@@ -2049,8 +2081,6 @@ __device__ __forceinline__ void item_slot(const KParams &P, const uint32_t *pc, 
         return;
     }
     if (t == 1) {  // BecomeLeader tla:157-173
-        if (role != CAN) return;
-        if (!(vp + 1 >= ((P.quirks & 1u) ? 1u : (uint32_t)(N / 2 + 1)))) return;  // (RaftSplitBrain: quorum 1)
         uint32_t mr = 0, nr = 0;
 #pragma unroll
         for (int u = 0; u < N; u++) {
@@ -2064,10 +2094,8 @@ __device__ __forceinline__ void item_slot(const KParams &P, const uint32_t *pc, 
         o.key = slot_key(s, BL, 0);
         return;
     }
-    if (role != LEA) return;
     if (t < 2 + (uint32_t)V) {  // ClientReq tla:233-240, witness v
         const uint32_t v = t - 2;
-        if ((misc >> (8 + v)) & 1u) return;  // valSent[v] # None
         o.misc = misc | (1u << (8 + v));
         o.lw = lw | ((ct | (v << 4)) << (8 * (ll + 1 - 2)));
         o.mirow = setnib(mirow, s, ll + 1);
@@ -2079,9 +2107,7 @@ __device__ __forceinline__ void item_slot(const KParams &P, const uint32_t *pc, 
         const uint32_t q = t - 2 - V;
         const uint32_t dst = q < s ? q : q + 1;
         const uint32_t ni = nib(nirow, dst);
-        if (!(ni <= ll + 1)) return;
         const uint32_t pb = s * N + dst;
-        if ((pend >> pb) & 1u) return;
         const uint32_t pli = ni - 1, plt = lw_term(lw, pli);
         const uint32_t ent = ni <= ll ? 1u : 0u;
         const uint32_t eb = ent ? lw_byte(lw, ni) : 0u;
@@ -2097,14 +2123,12 @@ __device__ __forceinline__ void item_slot(const KParams &P, const uint32_t *pc, 
     if (t == 2 + (uint32_t)V + (N - 1)) {  // LeaderCanCommit tla:398-407
         const uint32_t thr = P.seeded ? (uint32_t)N : (uint32_t)(N / 2 + 1);
         const uint32_t med = median_row<N>(mirow, thr);
-        if (!(med > ci)) return;
         o.w0 = row_w0(vf, ct, role, med, ll, s);
         o.key = slot_key(s, LCC, 0);
         return;
     }
     {  // Restart tla:409-414
         const uint32_t rc = (misc >> 4) & 15u;
-        if (!((int)rc < P.R)) return;
         o.w0 = row_w0(vf, ct, FOL, ci, ll, s);
         o.misc = (misc & ~0xF0u) | ((rc + 1) << 4);
         o.key = slot_key(s, RS, 0);
@@ -2167,7 +2191,7 @@ __device__ __forceinline__ uint32_t slot_class(uint32_t t) {
 // (the fused BecomeFollower kernel is not cut to RMC_FUSED_WAVES: at 4 waves per SIMD it spills 23 VGPRs, and with
 // the message-parent notes that build gave wrong BecomeFollower n3 counts while the uncut one matches the oracle --
 // profiles/r06_ab_message_parents.txt)
-template <int N, int V, int MR, bool BFV, bool FUSE, int PB>
+template <int N, int V, int MR, bool BFV, bool FUSE, int PB, int PF = 0>
 __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 && !BFV) ? RMC_FUSED_WAVES : 0) : (items_waves<N, V, MR, BFV>())) void k_expand_items(KParams P) {
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
@@ -2181,6 +2205,20 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
     constexpr int RC = FUSE ? 1 : 4;  // record words per lane in flight in the batch's copy (a fused batch: one)
     static_assert(S::MCAP + N * S::SLOTS_PER_SERVER <= NT, "a parent's items fit one evaluation round");
     static_assert(S::MCAP <= 128 && PB <= 64, "item codes: parent << 8 | slot bit << 7 | message index or s << 4 | t");
+    constexpr uint32_t SLOT_BITS = 12;
+    static_assert(S::SLOTS_PER_SERVER <= (int)SLOT_BITS && N * SLOT_BITS <= 64, "a server's slots: a bitmask in its part of sSlot's word");
+    static_assert(NT >= 64 && NT % 64 == 0, "the slot masks: a whole wave per server, lane j of it the batch's parent j");
+    // Item pre-filter (PF; a fused level lists every item whatever it says): an AppendResp whose HandleAppendResp
+    // guard fails is no item (har_guard), and of a server's slots only those whose guards hold without a lookup
+    // (slot_guard).  A dropped item is one for which the evaluation below leaves o.key, ob.key and akey at none:
+    // items of class IC_HAR have no BecomeFollower candidate (item_msg: ob needs m.term > currentTerm, which is
+    // IC_UT, or an AppendReq at a candidate in its term, which is IC_UT2) and raise no Assert (IC_UT2 alone);
+    // self-loops (FollowerAcceptEntry, IC_AE) are untouched.  Parents left without an item still get their counts
+    // and deadlock key from the rounds' loop.
+    // The switch is a template argument, and Launch::split picks the instantiation by KParams::prefilter: read
+    // from P here, both listings in one kernel cost the headline instantiation its bound (a VGPR spill and a
+    // private segment at 96 VGPRs; as an argument none -- profiles/item_prefilter_resources.txt).
+    constexpr uint32_t pf = FUSE ? 0u : (uint32_t)PF;
     __shared__ uint32_t sRec[PB * RECW];           // the batch's records, as in the ring
     __shared__ uint32_t sCore[PB * NWP];           // their nibble cores
     __shared__ uint8_t sMI[PB * S::MCAP];          // per message of the batch: its class (15: none)
@@ -2190,7 +2228,7 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
     __shared__ uint32_t sOff[PB];                  // record's first word in sRec
     __shared__ uint32_t sItm[PB + 1], sMsc[PB + 1];  // items / messages: exclusive scans over the batch
     __shared__ uint32_t sLive[PB];                 // per parent: messages some action may receive
-    __shared__ unsigned long long sSlot[PB];       // slot_range per server, 8 bits each
+    __shared__ unsigned long long sSlot[PB];       // per server the slots that are items, a bit each (SLOT_BITS per server)
     __shared__ uint32_t sCnt[PB], sAk[PB];         // enabled successors (self-loops apart), smallest Assert key
     __shared__ uint32_t sHo[FUSE ? 1 : PB];        // dense split chunk: each parent's first successor slot -- the
     __shared__ uint32_t sAlloc;                    // batch's successors packed from the start of its parents' sparse
@@ -2282,10 +2320,14 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
 #pragma unroll
                 for (int w = 0; w < NW; w++) sCore[tid * NWP + w] = c[w];
                 const uint32_t ec = c[Lo::W_MISC] & 15u, rc = (c[Lo::W_MISC] >> 4) & 15u;
-                unsigned long long sl = 0;
+                unsigned long long sl = 0;  // (pre-filter: the (parent, server) lanes' masks after the message pass)
+                if (!(pf & 1u)) {
 #pragma unroll
-                for (int s = 0; s < N; s++)
-                    sl |= (unsigned long long)slot_range<N, V>(nib(c[Lo::W_ROLE], s), ec, rc, P.E, P.R) << (8 * s);
+                    for (int s = 0; s < N; s++) {
+                        const uint32_t rg = slot_range<N, V>(nib(c[Lo::W_ROLE], s), ec, rc, P.E, P.R);
+                        sl |= (unsigned long long)(((1u << (rg >> 4)) - 1u) << (rg & 15u)) << (SLOT_BITS * s);
+                    }
+                }
                 sSlot[tid] = sl;
 #pragma unroll
                 for (int s = 0; s < N; s++) sVp[tid * N + s] = 0u;
@@ -2321,7 +2363,12 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
             const uint32_t *pc = sCore + j * NWP;
             const uint32_t ct = nib(pc[Lo::W_CT], dst);
             if (mi_type(inf) == VRESP && mi_term(inf) == ct) atomicAdd(&sVp[j * N + dst], 1u);
-            const uint32_t c = msg_class(inf, ct, nib(pc[Lo::W_ROLE], dst));
+            uint32_t c = msg_class(inf, ct, nib(pc[Lo::W_ROLE], dst));
+            if constexpr (!FUSE) {
+                if ((pf & 1u) && c == IC_HAR &&
+                    !har_guard<N>(pc[Lo::W_PEND], pc[Lo::W_MI + dst], pc[Lo::W_NI + dst], dst, inf))
+                    c = IC_DEAD;
+            }
             sMI[m] = (uint8_t)(c == IC_DEAD ? 15u : c);
             if constexpr (FUSE) sInf[m] = inf;
             if (c != IC_DEAD) atomicAdd(&sLive[j], 1u);
@@ -2342,14 +2389,28 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
             }
             P.hctx[(b0 + j) * (uint64_t)CTXW + k] = v;
         }
+        if (!FUSE && (pf & 1u)) {  // (one more barrier per batch, none per round)
+            // a lane per (parent, server): the slots whose guards hold (BecomeLeader's needs the votes counted above).
+            // A wave takes one server of all the parents: the server is wave-uniform (its shifts stay scalar; by
+            // lane the compiler kept a dozen lane constants live across the whole kernel), and a wave's lanes
+            // add to different words
+            const uint32_t j = (uint32_t)tid & 63u;
+            for (uint32_t u = __builtin_amdgcn_readfirstlane((uint32_t)tid >> 6); u < (uint32_t)N && j < nb; u += NT >> 6) {
+                const uint32_t *pc = sCore + j * NWP;
+                const uint32_t vp = sVp[j * N + u];
+                uint32_t mk = 0;
+#pragma unroll
+                for (uint32_t t = 0; t < (uint32_t)S::SLOTS_PER_SERVER; t++)
+                    mk |= slot_guard<N, V>(P, pc, vp, u, t) ? 1u << t : 0u;
+                if (mk) atomicOr(&sSlot[j], (unsigned long long)mk << (SLOT_BITS * u));
+            }
+            __syncthreads();
+        }
         // items per parent: its live messages and its slots; their scan (wave 0)
         if (tid < 64) {
             uint32_t ni = 0;
             if ((uint32_t)tid < nb) {
-                const unsigned long long sl = sSlot[tid];
-                ni = sLive[tid];
-#pragma unroll
-                for (int u = 0; u < N; u++) ni += (uint32_t)(sl >> (8 * u + 4)) & 15u;
+                ni = sLive[tid] + (uint32_t)__popcll(sSlot[tid]);
             }
             uint32_t ti;
             const uint32_t xi = wave_excl_scan(ni, tid, &ti);
@@ -2359,8 +2420,11 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
         if (tid < IC_N) sCc[tid] = 0u;
         __syncthreads();  // (also: the hash sums are read; sQ / sKey may reuse their words)
         PHASE(3);
+        PHASE_COUNT(0, 1u);
+        PHASE_COUNT(2, sItm[nb]);
         // (c) + (d): rounds of whole parents, up to NT items each
         for (uint32_t a = 0; a < nb;) {
+            PHASE_COUNT(1, 1u);
             const uint32_t ibase = sItm[a];
             uint32_t b = a;  // the last parent b with sItm[b] <= ibase + NT: parents a .. b - 1 fit
 #pragma unroll
@@ -2380,14 +2444,14 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
             }
             for (uint32_t q = (uint32_t)tid; q < (b - a) * (uint32_t)N; q += NT) {  // a lane per (parent, server)
                 const uint32_t j = a + q / N, u = q % N;
-                const uint32_t rg = (uint32_t)(sSlot[j] >> (8 * u)) & 0xFFu, n = rg >> 4, t0 = rg & 15u;
+                const uint32_t mk = (uint32_t)(sSlot[j] >> (SLOT_BITS * u)) & ((1u << SLOT_BITS) - 1u);
                 uint32_t pos[S::SLOTS_PER_SERVER];
 #pragma unroll
-                for (uint32_t r = 0; r < (uint32_t)S::SLOTS_PER_SERVER; r++)
-                    if (r < n) pos[r] = atomicAdd(&sCc[slot_class<N, V>(t0 + r)], 1u);
+                for (uint32_t t = 0; t < (uint32_t)S::SLOTS_PER_SERVER; t++)
+                    if ((mk >> t) & 1u) pos[t] = atomicAdd(&sCc[slot_class<N, V>(t)], 1u);
 #pragma unroll
-                for (uint32_t r = 0; r < (uint32_t)S::SLOTS_PER_SERVER; r++)
-                    if (r < n) sQ[slot_class<N, V>(t0 + r) * NT + pos[r]] = (uint16_t)((j << 8) | 0x80u | (u << 4) | (t0 + r));
+                for (uint32_t t = 0; t < (uint32_t)S::SLOTS_PER_SERVER; t++)
+                    if ((mk >> t) & 1u) sQ[slot_class<N, V>(t) * NT + pos[t]] = (uint16_t)((j << 8) | 0x80u | (u << 4) | t);
             }
             __syncthreads();
             PHASE(7);
@@ -4364,8 +4428,10 @@ struct Launch {
     // ceil(batches / grid) of them or one fewer)
     static void split(const KParams &P, unsigned grid, hipStream_t s) {
         const uint64_t nbat = (P.p_end - P.p_begin + XB_PARENTS - 1) / XB_PARENTS;
-        hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, false, XB_PARENTS>), dim3(items_grid(nbat, grid)),
-                           dim3(items_threads<N, V, MR, false>()), 0, s, P);
+        // (the item pre-filter's setting is an instantiation each: KParams::prefilter, RMC_ITEM_PREFILTER)
+        auto k = P.prefilter ? k_expand_items<N, V, MR, BFV, false, XB_PARENTS, 1>
+                             : k_expand_items<N, V, MR, BFV, false, XB_PARENTS, 0>;
+        hipLaunchKernelGGL(k, dim3(items_grid(nbat, grid)), dim3(items_threads<N, V, MR, false>()), 0, s, P);
     }
     static unsigned items_grid(uint64_t nbat, unsigned grid) {
         const uint64_t cap = grid ? grid : 2048u;
@@ -4374,7 +4440,11 @@ struct Launch {
     // blocks per CU of the split expansion and of the split items commit (0: k_commit_split commits)
     static hipError_t items_blocks(int *expand, int *commit) {
         *commit = 0;
-        hipError_t e = resident_blocks(k_expand_items<N, V, MR, BFV, false, XB_PARENTS>, items_threads<N, V, MR, false>(), expand);
+        // (the fewer of the pre-filter's two instantiations: the same wherever items_waves cuts the registers)
+        int x1 = 0;
+        hipError_t e = resident_blocks(k_expand_items<N, V, MR, BFV, false, XB_PARENTS, 0>, items_threads<N, V, MR, false>(), expand);
+        if (e == hipSuccess) e = resident_blocks(k_expand_items<N, V, MR, BFV, false, XB_PARENTS, 1>, items_threads<N, V, MR, false>(), &x1);
+        if (e == hipSuccess) *expand = std::min(*expand, x1);
         if constexpr (MX <= XB_THREADS) {
             if (e == hipSuccess) e = resident_blocks(k_commit_items<N, V, MR, MX, false, 64, false>, XB_THREADS, commit);
         }

@@ -40,5 +40,5 @@ mkdir -p "$OUT"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DRMC_WITH_RCCL $FLAGS -Iinclude -I../include -Icsrc \
   -c csrc/rmc_kernels.hip -o "$OUT/rmc_kernels.o"
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/librmc.so" "$OUT/rmc_kernels.o" build/rmc_engine.o build/rmc_cfg.o build/rmc_probe.o -lrccl
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/librmc.so" "$OUT/rmc_kernels.o" build/rmc_engine.o build/rmc_graph.o build/rmc_cfg.o build/rmc_probe.o -lrccl
 echo "$OUT/librmc.so"

@@ -25,8 +25,9 @@ NAMES = ["load parent", "evaluate actions", "ranks + error keys", "staging", "ha
          "signatures, coset ranks", "hash tasks (coset minimum)", "seen-set probe + election (fused)",
          # k_commit (slots 8-15)
          "commit: header wait (+ parents w/o winners)", "commit: record + election words + staged rows",
-         "commit: winner test", "-", "commit: rebuild, encode, seen insert, trace, invariants",
-         "commit: scan + record writes", "-", "-"]
+         "commit: winner test", "(count) k_expand_items batches", "commit: rebuild, encode, seen insert, trace, invariants",
+         "commit: scan + record writes", "(count) k_expand_items item rounds", "(count) k_expand_items items listed"]
+COUNTS = (11, 14, 15)  # not clocks: what k_expand_items listed (batches of 64 parents, rounds of <= 256 items)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("n", type=int)
@@ -60,8 +61,11 @@ lib.rmc_debug_phases(buf, 0)
 res = mc.result()
 print(f"config n{a.n}_v{a.V}_e{a.E}_r{a.R}: {lv} levels, {res.distinct} distinct, {el:.2f} s")
 for lo, what in ((0, "k_expand"), (8, "k_commit")):
-    tot = sum(buf[lo:lo + 8]) or 1
+    tot = sum(buf[i] for i in range(lo, lo + 8) if i not in COUNTS) or 1
     print(f" {what}: share of its waves' time")
     for i in range(lo, lo + 8):
-        if buf[i]:
+        if buf[i] and i not in COUNTS:
             print(f"  {i} {NAMES[i]:46s} {100.0 * buf[i] / tot:6.2f} %  ({buf[i] / 1e9:.2f} G wave-clocks)")
+if buf[11]:
+    print(f" k_expand_items: {buf[11]} batches, {buf[14]} item rounds, {buf[15]} items listed: "
+          f"{buf[15] / buf[11]:.1f} items and {buf[14] / buf[11]:.2f} rounds per batch")
