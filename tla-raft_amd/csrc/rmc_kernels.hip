@@ -956,46 +956,33 @@ __device__ __forceinline__ void fetch_record(const KParams &P, uint64_t start, i
     rw1 = (MR > 1 && 64 + lane < RECW_MAX) ? ring_word(P.front, start, 64u + (uint32_t)lane, P.rcap) : 0u;
 }
 
-// load_parent on a record already fetched (fetch_record)
-template <int N, int V, int MR, bool SUMS>
-__device__ __forceinline__ void load_parent_words(const KParams &P, uint64_t start, uint32_t rw0, uint32_t rw1, int lane,
-                                                  Wave<N, V, MR> &W, uint64_t *M0, uint64_t *M1, uint32_t *pcore) {
+// The core of a fetched record: its first CCW words read across the lanes (wave-uniform), decoded.
+template <int N, int V>
+__device__ __forceinline__ void record_core(uint32_t rw0, uint32_t *c) {
+    constexpr int CCW = Codec<N, V>::CCW;
+    uint32_t packed[CCW];
+#pragma unroll
+    for (int k = 0; k < CCW; k++) packed[k] = rdlane(rw0, k);
+    decode_core<N, V>(packed, c);
+}
+
+// Message id k of a fetched record, every lane its own k: the record word that holds it (CCW + k / 2)
+// shuffled from its lane, then the half.  All lanes call it (a shuffle); k past the record's ids
+// gives a value the caller drops.
+template <int N, int V, int MR>
+__device__ __forceinline__ uint32_t record_id(uint32_t rw0, uint32_t rw1, uint32_t k) {
+    const uint32_t wi = (uint32_t)Codec<N, V>::CCW + (k >> 1);
+    const uint32_t a = __shfl(rw0, (int)(wi & 63u), 64);
+    const uint32_t b = MR > 1 ? __shfl(rw1, (int)(wi & 63u), 64) : 0u;
+    const uint32_t word = wi < 64u ? a : b;
+    return (word >> ((k & 1u) * 16u)) & 0xFFFFu;
+}
+
+// Per server s, the VoteResps to s at its current term among the wave's messages (BecomeLeader's
+// quorum, tla:160-164), to pcore[NW + s].
+template <int N, int V, int MR>
+__device__ __forceinline__ void vote_counts(const Wave<N, V, MR> &W, int lane, uint32_t *pcore) {
     using Lo = Layout<N, V>;
-    using S = Spec<N, V, MR>;
-    uint32_t packed[S::CCW];
-#pragma unroll
-    for (int k = 0; k < S::CCW; k++) packed[k] = rdlane(rw0, k);
-    decode_core<N, V>(packed, W.c);
-    if (lane == 0) {  // uniform values: one lane writes the LDS copy (no runtime-indexed register array)
-#pragma unroll
-        for (int w = 0; w < Lo::NW; w++) pcore[w] = W.c[w];
-    }
-    W.lds = pcore;
-    W.nm = (W.c[Lo::W_MISC] >> 16) & 0xFFu;
-    W.idw = ring_wrap(start + S::CCW, P.rcap);
-    if (SUMS && lane < N * N) { M0[lane] = 0; M1[lane] = 0; }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < MR; r++) {
-        const uint32_t k = (uint32_t)(r * 64 + lane);
-        const uint32_t wi = (uint32_t)S::CCW + (k >> 1);  // record word holding id k
-        const uint32_t a = __shfl(rw0, (int)(wi & 63u), 64);
-        const uint32_t b = MR > 1 ? __shfl(rw1, (int)(wi & 63u), 64) : 0u;
-        const uint32_t word = wi < 64u ? a : b;
-        uint32_t id = 0xFFFFu, inf = 0;
-        if (k < W.nm) {
-            id = (word >> ((k & 1u) * 16u)) & 0xFFFFu;
-            inf = P.t.info[id];
-            if (SUMS) {
-                const ulonglong2 g = P.t.gmsg[id];
-                const uint32_t pr = mi_src(inf) * N + mi_dst(inf);
-                atomicAdd((unsigned long long *)&M0[pr], (unsigned long long)g.x);
-                atomicAdd((unsigned long long *)&M1[pr], (unsigned long long)g.y);
-            }
-        }
-        W.id[r] = id;
-        W.inf[r] = inf;
-    }
 #pragma unroll
     for (int s = 0; s < N; s++) {
         const uint32_t ct = nib(W.c[Lo::W_CT], s);
@@ -1009,6 +996,43 @@ __device__ __forceinline__ void load_parent_words(const KParams &P, uint64_t sta
         }
         if (lane == 0) pcore[Lo::NW + s] = cnt;
     }
+}
+
+// load_parent on a record already fetched (fetch_record)
+template <int N, int V, int MR, bool SUMS>
+__device__ __forceinline__ void load_parent_words(const KParams &P, uint64_t start, uint32_t rw0, uint32_t rw1, int lane,
+                                                  Wave<N, V, MR> &W, uint64_t *M0, uint64_t *M1, uint32_t *pcore) {
+    using Lo = Layout<N, V>;
+    using S = Spec<N, V, MR>;
+    record_core<N, V>(rw0, W.c);
+    if (lane == 0) {  // uniform values: one lane writes the LDS copy (no runtime-indexed register array)
+#pragma unroll
+        for (int w = 0; w < Lo::NW; w++) pcore[w] = W.c[w];
+    }
+    W.lds = pcore;
+    W.nm = (W.c[Lo::W_MISC] >> 16) & 0xFFu;
+    W.idw = ring_wrap(start + S::CCW, P.rcap);
+    if (SUMS && lane < N * N) { M0[lane] = 0; M1[lane] = 0; }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < MR; r++) {
+        const uint32_t k = (uint32_t)(r * 64 + lane);
+        const uint32_t rid = record_id<N, V, MR>(rw0, rw1, k);
+        uint32_t id = 0xFFFFu, inf = 0;
+        if (k < W.nm) {
+            id = rid;
+            inf = P.t.info[id];
+            if (SUMS) {
+                const ulonglong2 g = P.t.gmsg[id];
+                const uint32_t pr = mi_src(inf) * N + mi_dst(inf);
+                atomicAdd((unsigned long long *)&M0[pr], (unsigned long long)g.x);
+                atomicAdd((unsigned long long *)&M1[pr], (unsigned long long)g.y);
+            }
+        }
+        W.id[r] = id;
+        W.inf[r] = inf;
+    }
+    vote_counts<N, V, MR>(W, lane, pcore);
     __syncthreads();
 }
 
@@ -1024,23 +1048,17 @@ struct MsgPre {
 template <int N, int V, int MR>
 __device__ __forceinline__ void fetch_msgs(const KParams &P, uint32_t rw0, uint32_t rw1, int lane, MsgPre<MR> &pm) {
     using Lo = Layout<N, V>;
-    using S = Spec<N, V, MR>;
-    uint32_t packed[S::CCW], c[Lo::NW];
-#pragma unroll
-    for (int k = 0; k < S::CCW; k++) packed[k] = rdlane(rw0, k);
-    decode_core<N, V>(packed, c);
+    uint32_t c[Lo::NW];
+    record_core<N, V>(rw0, c);
     const uint32_t nm = (c[Lo::W_MISC] >> 16) & 0xFFu;
 #pragma unroll
     for (int r = 0; r < MR; r++) {
         const uint32_t k = (uint32_t)(r * 64 + lane);
-        const uint32_t wi = (uint32_t)S::CCW + (k >> 1);
-        const uint32_t a = __shfl(rw0, (int)(wi & 63u), 64);
-        const uint32_t b = MR > 1 ? __shfl(rw1, (int)(wi & 63u), 64) : 0u;
-        const uint32_t word = wi < 64u ? a : b;
+        const uint32_t rid = record_id<N, V, MR>(rw0, rw1, k);
         uint32_t id = 0xFFFFu, inf = 0;
         ulonglong2 g = make_ulonglong2(0ull, 0ull);
         if (k < nm) {
-            id = (word >> ((k & 1u) * 16u)) & 0xFFFFu;
+            id = rid;
             inf = P.t.info[id];
             g = P.t.gmsg[id];
         }
@@ -1057,10 +1075,7 @@ __device__ __forceinline__ void load_parent_pre(const KParams &P, uint64_t start
                                                 const MsgPre<MR> &pm) {
     using Lo = Layout<N, V>;
     using S = Spec<N, V, MR>;
-    uint32_t packed[S::CCW];
-#pragma unroll
-    for (int k = 0; k < S::CCW; k++) packed[k] = rdlane(rw0, k);
-    decode_core<N, V>(packed, W.c);
+    record_core<N, V>(rw0, W.c);
     if (lane == 0) {
 #pragma unroll
         for (int w = 0; w < Lo::NW; w++) pcore[w] = W.c[w];
@@ -1081,19 +1096,7 @@ __device__ __forceinline__ void load_parent_pre(const KParams &P, uint64_t start
         W.id[r] = pm.id[r];
         W.inf[r] = pm.inf[r];
     }
-#pragma unroll
-    for (int s = 0; s < N; s++) {
-        const uint32_t ct = nib(W.c[Lo::W_CT], s);
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int r = 0; r < MR; r++) {
-            const uint32_t m = W.inf[r];
-            const bool hit = (uint32_t)(r * 64 + lane) < W.nm && mi_type(m) == VRESP && mi_dst(m) == (uint32_t)s &&
-                             mi_term(m) == ct;
-            cnt += (uint32_t)__popcll(__ballot(hit));
-        }
-        if (lane == 0) pcore[Lo::NW + s] = cnt;
-    }
+    vote_counts<N, V, MR>(W, lane, pcore);
     __syncthreads();
 }
 
@@ -1456,6 +1459,100 @@ __device__ __forceinline__ uint32_t probe_elect(const KParams &P, const ulonglon
     return seen_contains(P.seen, f) ? LS_SEEN : elect_slot<MX>(P.ET, P.wacc, Lmask, P.epoch, f, q, e, g, v0);
 }
 
+// ---- the steps the wave-per-parent kernels share (k_expand, k_walk, k_cover, k_edges) ----------------
+// A lane holds NC = MR + 1 (+ MR with BecomeFollower) candidates: its message of every round, its
+// non-message slot, its messages' BecomeFollower successors.
+
+// Evaluate a loaded parent on the lanes.  ainf: where the info words of the messages each candidate
+// adds go ((MR + 1) * 64 * NADD words, k_expand's hash inputs), or nullptr.
+// (__restrict__: the parent, the candidates and the Assert key are separate locals of every caller.  Said
+// here, the function is optimized on its own as its body was inside each kernel: without it k_edges and
+// k_expand instantiations take up to 36 VGPRs more, one k_edges a wave per SIMD less.)
+template <int N, int V, int MR, bool BFV, int NC>
+__device__ __forceinline__ void wave_eval(const KParams &P, const Wave<N, V, MR> &__restrict__ W, int lane,
+                                          Succ<N, V, MR> (&__restrict__ cand)[NC], uint32_t &__restrict__ akey,
+                                          uint32_t *ainf) {
+    using S = Spec<N, V, MR>;
+    static_assert(NC == MR + 1 + (BFV ? MR : 0), "candidates per lane");
+    // the lane index, opaque to the compiler here: what the evaluation derives from it is
+    // recomputed per parent instead of hoisted out of the caller's loop (and spilled)
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    // every id lookup of the actions in one round trip (msg_nat / slot_nats)
+    uint32_t mid[MR], sid[N - 1];
+    {
+        uint32_t snat[N - 1];
+        slot_nats<N, V, MR>(P, W, ln, snat);
+#pragma unroll
+        for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
+#pragma unroll
+        for (int i = 0; i < N - 1; i++) sid[i] = nat_lookup(P, snat[i]);
+    }
+#pragma unroll
+    for (int r = 0; r < MR; r++)
+        eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey,
+                                ainf ? &ainf[(r * 64 + ln) * S::NADD] : nullptr, mid[r]);
+    eval_slot<N, V, MR>(P, W, ln, cand[MR], ainf ? &ainf[(MR * 64 + ln) * S::NADD] : nullptr, sid);
+}
+
+// The lanes that hold an enabled candidate, per candidate; returns how many there are in the wave.
+template <int N, int V, int MR, int NC>
+__device__ __forceinline__ uint32_t wave_enabled(const Succ<N, V, MR> (&cand)[NC], uint64_t (&en)[NC]) {
+    uint32_t total = 0;
+#pragma unroll
+    for (int r = 0; r < NC; r++) {
+        en[r] = __ballot(cand[r].key != KEY_NONE);
+        total += (uint32_t)__popcll(en[r]);
+    }
+    return total;
+}
+
+// Rank of every enabled candidate in TLC order: the enabled slot keys below its own (slot keys are
+// distinct and increase in TLC order, Next tla:416-430).
+template <int N, int V, int MR, int NC>
+__device__ __forceinline__ void wave_ranks(const Succ<N, V, MR> (&cand)[NC], const uint64_t (&en)[NC],
+                                           uint32_t (&rank)[NC]) {
+#pragma unroll
+    for (int r = 0; r < NC; r++) rank[r] = 0;
+#pragma unroll
+    for (int q = 0; q < NC; q++) {
+        for (uint64_t m = en[q]; m; m &= m - 1) {
+            const int t = __ffsll((unsigned long long)m) - 1;
+            const uint32_t kt = rdlane(cand[q].key, t);
+#pragma unroll
+            for (int r = 0; r < NC; r++) rank[r] += kt < cand[r].key ? 1u : 0u;
+        }
+    }
+}
+
+// The capacity rule: some enabled successor's message set is past the MCAP ids a record holds
+// (wave-uniform; what follows from it is the caller's).
+template <int N, int V, int MR, int NC>
+__device__ __forceinline__ bool wave_overflow(const Wave<N, V, MR> &W, const Succ<N, V, MR> (&cand)[NC]) {
+    bool ovf = false;
+#pragma unroll
+    for (int r = 0; r < NC; r++)
+        ovf |= cand[r].key != KEY_NONE && W.nm + cand[r].nadd > (uint32_t)Spec<N, V, MR>::MCAP;
+    return __ballot(ovf) != 0ull;
+}
+
+// The one candidate of rank idx: ch is each lane's own copy of it, the result the lane that holds
+// it -- or -1 (unreachable: the ranks are a permutation of 0 .. total - 1).
+template <int N, int V, int MR, int NC>
+__device__ __forceinline__ int wave_pick(const Succ<N, V, MR> (&cand)[NC], const uint32_t (&rank)[NC], uint32_t idx,
+                                         Succ<N, V, MR> &ch) {
+    ch = cand[MR];
+    bool hit = false;
+#pragma unroll
+    for (int r = 0; r < NC; r++) {
+        const bool h = cand[r].key != KEY_NONE && rank[r] == idx;
+        if (h) ch = cand[r];
+        hit |= h;
+    }
+    const uint64_t hm = __ballot(hit);
+    return hm ? __ffsll((unsigned long long)hm) - 1 : -1;
+}
+
 template <int N, int MR, int MODE, bool BFV>
 constexpr int expand_waves() {
     return (N <= 3 && MR == 1 && !BFV) ? RMC_N3_WAVES : ((BFV && N >= 4) ? 1 : RMC_WIDE_WAVES);
@@ -1537,25 +1634,7 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
         PHASE(0);
         Succ<N, V, MR> cand[NC];
         uint32_t akey = KEY_NONE;
-        // the lane index, opaque to the compiler here: what the evaluation derives from it is
-        // recomputed per parent instead of hoisted out of the loop (and spilled)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        // every id lookup of the actions in one round trip (msg_nat / slot_nats)
-        uint32_t mid[MR], sid[N - 1];
-        {
-            uint32_t snat[N - 1];
-            slot_nats<N, V, MR>(P, W, ln, snat);
-#pragma unroll
-            for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
-#pragma unroll
-            for (int i = 0; i < N - 1; i++) sid[i] = nat_lookup(P, snat[i]);
-        }
-#pragma unroll
-        for (int r = 0; r < MR; r++)
-            eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey,
-                                    &sAinf[(r * 64 + ln) * S::NADD], mid[r]);
-        eval_slot<N, V, MR>(P, W, ln, cand[MR], &sAinf[(MR * 64 + ln) * S::NADD], sid);
+        wave_eval<N, V, MR, BFV>(P, W, lane, cand, akey, sAinf);
         if constexpr (PREM) {
             if (more) fetch_msgs<N, V, MR>(P, nrw0, nrw1, lane, pm);
         } else {
@@ -1564,24 +1643,9 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
         PHASE(1);
         // rank of every enabled successor in TLC order
         uint64_t en[NC];
-        uint32_t total = 0;
-#pragma unroll
-        for (int r = 0; r < NC; r++) {
-            en[r] = __ballot(cand[r].key != KEY_NONE);
-            total += (uint32_t)__popcll(en[r]);
-        }
+        const uint32_t total = wave_enabled<N, V, MR>(cand, en);
         uint32_t rank[NC];
-#pragma unroll
-        for (int r = 0; r < NC; r++) rank[r] = 0;
-#pragma unroll
-        for (int q = 0; q < NC; q++) {
-            for (uint64_t m = en[q]; m; m &= m - 1) {
-                const int t = __ffsll((unsigned long long)m) - 1;
-                const uint32_t kt = rdlane(cand[q].key, t);
-#pragma unroll
-                for (int r = 0; r < NC; r++) rank[r] += kt < cand[r].key ? 1u : 0u;
-            }
-        }
+        wave_ranks<N, V, MR>(cand, en, rank);
         // a sharded round routes every successor's fingerprint to its owner, self-loops (the parent itself,
         // FollowerAcceptEntry changing nothing) too; they are counted for the level statistics only
         if (MODE == M_FUSED) {
@@ -1591,10 +1655,7 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
         const uint64_t pl = p - P.p_begin;  // chunk-local parent index
         uint64_t am = 0;
         {
-            bool ovf = false;
-#pragma unroll
-            for (int r = 0; r < NC; r++) ovf |= cand[r].key != KEY_NONE && W.nm + cand[r].nadd > (uint32_t)S::MCAP;
-            if (__ballot(ovf) && lane == 0) atomicOr(&P.flags[0], 1u);
+            if (wave_overflow<N, V, MR>(W, cand) && lane == 0) atomicOr(&P.flags[0], 1u);
             am = __ballot(akey != KEY_NONE);
             if (am) {
                 uint32_t best = KEY_NONE;
@@ -3225,6 +3286,70 @@ __device__ __forceinline__ bool last_commit_block(uint32_t *tick, uint32_t nb) {
     return __builtin_amdgcn_readfirstlane(last) != 0;
 }
 
+// ---- what every commit leaves behind for a winner (k_commit, k_commit_split, k_commit_items) ---------
+// Publish the winner `c` (successor `key` of parent p, next-level index `out`, a record of `size`
+// words): its trace entry -- in a sharded round the sidecar that travels with the record to the
+// state's next-level owner (the owner already inserted the fingerprint) -- and the INVARIANTs
+// (Raft.cfg:33), the smallest (parent, key) that fails going to ERR_INV / ERR_EVAL.  A violation is
+// not an error once ERR_NSLOTS is set (-continue: k_viol_scan counts them).  msg_view() gives the
+// caller's view of the winner's message ids; it is asked for after the trace entry is written, where
+// the commits built it (k_commit_items' reads the frontier for it).
+template <int N, int V, class FM>
+__device__ __forceinline__ void publish_winner(const KParams &P, uint64_t p, uint64_t out, uint32_t key, uint32_t size,
+                                               bool route, const uint32_t *c, FM &&msg_view) {
+    if (route) {
+        const uint64_t pref = P.gid_parent_base + p;
+        P.xside[out] = make_uint4((uint32_t)pref, (uint32_t)(pref >> 32), key, size);
+    } else {
+        const uint64_t gid = P.gid_next_base + out;
+        P.par[gid - P.trace_base] = P.gid_parent_base + p;
+        P.pslot[gid - P.trace_base] = (uint16_t)key;
+    }
+    int which = 0;
+    const MsgView mv = msg_view();
+    const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
+    if (iv != 1 && !(iv == 0 && P.err[ERR_NSLOTS])) {
+        const unsigned long long ek = ((((unsigned long long)p << 16) | key) << 8) | (unsigned long long)which;
+        atomicMin(&P.err[iv == 0 ? ERR_INV : ERR_EVAL], ek);
+    }
+}
+
+// A winner's message ids, written by its own lane at ring position oid: the parent's nm sorted ids
+// (parent_id(k), asked for in order) merged with the nadd added ones (sorted here: BecomeCandidate
+// adds its VoteReqs in peer order), a word at a time, the last half-word padded.
+template <int NADD, class F>
+__device__ __forceinline__ void merge_ids_lane(uint32_t *next, uint64_t oid, uint64_t rcap, uint32_t nm, uint32_t (&add)[4],
+                                               uint32_t nadd, F &&parent_id) {
+#pragma unroll
+    for (int x = 0; x < NADD; x++)
+#pragma unroll
+        for (int y = 0; y + 1 < NADD - x; y++)
+            if ((uint32_t)(y + 1) < nadd && add[y + 1] < add[y]) {
+                const uint32_t t = add[y];
+                add[y] = add[y + 1];
+                add[y + 1] = t;
+            }
+    uint32_t kk = 0, ai = 0, word = 0;
+    const uint32_t tot_ids = nm + nadd;
+    for (uint32_t o = 0; o < tot_ids; o++) {
+        uint32_t next_add = 0xFFFFFFFFu;
+#pragma unroll
+        for (int y = 0; y < NADD; y++) next_add = (uint32_t)y == ai ? add[y] : next_add;
+        const uint32_t pv = kk < nm ? parent_id(kk) : 0xFFFFFFFFu;
+        uint32_t id;
+        if (ai < nadd && next_add < pv) {
+            id = next_add;
+            ai++;
+        } else {
+            id = pv;
+            kk++;
+        }
+        if (o & 1u) next[ring_wrap(oid + (o >> 1), rcap)] = word | (id << 16);
+        else word = id;
+    }
+    if (tot_ids & 1u) next[ring_wrap(oid + (tot_ids >> 1), rcap)] = word;
+}
+
 // One wave per parent with winners: rebuild each winner (in TLC order) from the parent's core and
 // its staged row, check the INVARIANTs (Raft.cfg:33) on it, append it to the next level (record
 // at the scanned word offset, its offset in noff), insert its fingerprint, record its parent
@@ -3306,9 +3431,8 @@ __global__ __launch_bounds__(64, (N <= 3 && MR == 1) ? RMC_N3_COMMIT_WAVES : 1) 
         const uint64_t start = ring_wrap(P.fbase + foffp, P.rcap);
         // the parent's record in one round trip (as load_parent), and with it the election words
         // of the first 64 slots (their indices came with the first round trip)
-        const uint32_t rw0 = lane < S::RECW_MAX ? ring_word(P.front, start, (uint32_t)lane, P.rcap) : 0u;
-        const uint32_t rw1 =
-            (MR > 1 && 64 + lane < S::RECW_MAX) ? ring_word(P.front, start, 64u + (uint32_t)lane, P.rcap) : 0u;
+        uint32_t rw0, rw1;
+        fetch_record<MR, S::RECW_MAX>(P, start, lane, rw0, rw1);
         // (slots past the parent's t successors hold a stale lslot from an earlier chunk: never an index)
         // (verdicts in lslot -- sharded round, or a split chunk after k_insert_winners -- need no election word)
         const bool verdict = P.route || (P.split & 4);
@@ -3323,20 +3447,16 @@ __global__ __launch_bounds__(64, (N <= 3 && MR == 1) ? RMC_N3_COMMIT_WAVES : 1) 
             xb = src[1];
             if (S::SW4 > 2) xc = src[2];
         }
-        uint32_t pc[Lo::NW], ppk[S::CCW];
-#pragma unroll
-        for (int k = 0; k < S::CCW; k++) ppk[k] = rdlane(rw0, k);
-        decode_core<N, V>(ppk, pc);
+        uint32_t pc[Lo::NW];
+        record_core<N, V>(rw0, pc);
         const uint32_t nm = (pc[Lo::W_MISC] >> 16) & 0xFFu;
         const uint64_t idw = ring_wrap(start + S::CCW, P.rcap);
         uint32_t id[MR];
 #pragma unroll
         for (int r = 0; r < MR; r++) {
             const uint32_t k = (uint32_t)(r * 64 + lane);
-            const uint32_t wi = (uint32_t)S::CCW + (k >> 1);
-            const uint32_t a = __shfl(rw0, (int)(wi & 63u), 64);
-            const uint32_t b = MR > 1 ? __shfl(rw1, (int)(wi & 63u), 64) : 0u;
-            id[r] = k < nm ? (((wi < 64u ? a : b) >> ((k & 1u) * 16u)) & 0xFFFFu) : 0xFFFFu;
+            const uint32_t rid = record_id<N, V, MR>(rw0, rw1, k);
+            id[r] = k < nm ? rid : 0xFFFFu;
         }
         PHASE(1);
         const uint32_t w0 = bo + wp;
@@ -3378,24 +3498,10 @@ __global__ __launch_bounds__(64, (N <= 3 && MR == 1) ? RMC_N3_COMMIT_WAVES : 1) 
                 const uint32_t key = sb.z & 0xFFFFu, nadd = sb.z >> 16;
                 size = (uint32_t)S::CCW + ((nm + nadd + 1u) >> 1);
                 const uint64_t out = P.next_base + w0 + done + (uint32_t)__popcll(m & lt_mask);
-                if (P.route) {
-                    // sharded round: the owner already inserted the fingerprint; the trace entry
-                    // travels with the record to the state's next-level owner
-                    const uint64_t pref = P.gid_parent_base + p;
-                    P.xside[out] = make_uint4((uint32_t)pref, (uint32_t)(pref >> 32), key, size);
-                } else {
-                    const uint64_t gid = P.gid_next_base + out;
-                    if (!(P.split & 2)) seen_insert(P.seen, P.fp[q]);  // (split chunk: k_insert_winners)
-                    P.par[gid - P.trace_base] = P.gid_parent_base + p;
-                    P.pslot[gid - P.trace_base] = (uint16_t)key;
-                }
-                int which = 0;
-                const MsgView mv{P.front, idw, P.rcap, nm, sb.w, sc.x, nadd, P.t.info};
-                const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
-                if (iv != 1 && !(iv == 0 && P.err[ERR_NSLOTS])) {
-                    const unsigned long long ek = ((((unsigned long long)p << 16) | key) << 8) | (unsigned long long)which;
-                    atomicMin(&P.err[iv == 0 ? ERR_INV : ERR_EVAL], ek);
-                }
+                // (sharded round: the owner inserted the fingerprint; split chunk: k_insert_winners)
+                if (!P.route && !(P.split & 2)) seen_insert(P.seen, P.fp[q]);
+                publish_winner<N, V>(P, p, out, key, size, P.route != 0, c,
+                                     [&] { return MsgView{P.front, idw, P.rcap, nm, sb.w, sc.x, nadd, P.t.info}; });
             }
             PHASE(4);
             uint32_t wtot;
@@ -3525,56 +3631,16 @@ __global__ __launch_bounds__(256) void k_commit_split(KParams P) {
             P.noff[out] = wd;
 #pragma unroll
             for (int w = 0; w < CCW; w++) P.next[ring_wrap(rs + (uint32_t)w, P.rcap)] = pk[w];
-            // the parent's sorted ids merged with the added ones (sorted here: BecomeCandidate adds
-            // its VoteReqs in peer order), written a word at a time, the last half-word padded
+            // the parent's ids from the ring, a word per two ids
             uint32_t add[4] = {sb.w & 0xFFFFu, sb.w >> 16, sc.x & 0xFFFFu, sc.x >> 16};
-#pragma unroll
-            for (int a = 0; a < S::NADD; a++)
-#pragma unroll
-                for (int b = 0; b + 1 < S::NADD - a; b++)
-                    if ((uint32_t)(b + 1) < nadd && add[b + 1] < add[b]) {
-                        const uint32_t x = add[b];
-                        add[b] = add[b + 1];
-                        add[b + 1] = x;
-                    }
-            const uint64_t pid = ring_wrap(start + CCW, P.rcap), oid = ring_wrap(rs + CCW, P.rcap);
-            uint32_t kk = 0, a = 0, word = 0, pw = 0;
-            const uint32_t tot_ids = nm + nadd;
-            for (uint32_t o = 0; o < tot_ids; o++) {
-                uint32_t next_add = 0xFFFFFFFFu;
-#pragma unroll
-                for (int b = 0; b < S::NADD; b++) next_add = (uint32_t)b == a ? add[b] : next_add;
-                if (kk < nm && (kk & 1u) == 0u) pw = ring_word(P.front, pid, kk >> 1, P.rcap);
-                const uint32_t pv = (pw >> ((kk & 1u) * 16u)) & 0xFFFFu;
-                uint32_t id;
-                if (a < nadd && (kk >= nm || next_add < pv)) {
-                    id = next_add;
-                    a++;
-                } else {
-                    id = pv;
-                    kk++;
-                }
-                if (o & 1u) P.next[ring_wrap(oid + (o >> 1), P.rcap)] = word | (id << 16);
-                else word = id;
-            }
-            if (tot_ids & 1u) P.next[ring_wrap(oid + (tot_ids >> 1), P.rcap)] = word;
-            const uint32_t key = sb.z & 0xFFFFu;
-            if (P.route) {
-                // sharded round: the trace entry travels with the record to the state's next-level owner
-                const uint64_t pref = P.gid_parent_base + p;
-                P.xside[out] = make_uint4((uint32_t)pref, (uint32_t)(pref >> 32), key, size);
-            } else {
-                const uint64_t gid = P.gid_next_base + out;
-                P.par[gid - P.trace_base] = P.gid_parent_base + p;
-                P.pslot[gid - P.trace_base] = (uint16_t)key;
-            }
-            int which = 0;
-            const MsgView mv{P.front, pid, P.rcap, nm, sb.w, sc.x, nadd, P.t.info};
-            const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
-            if (iv != 1 && !(iv == 0 && P.err[ERR_NSLOTS])) {
-                const unsigned long long ek = ((((unsigned long long)p << 16) | key) << 8) | (unsigned long long)which;
-                atomicMin(&P.err[iv == 0 ? ERR_INV : ERR_EVAL], ek);
-            }
+            const uint64_t pid = ring_wrap(start + CCW, P.rcap);
+            merge_ids_lane<S::NADD>(P.next, ring_wrap(rs + CCW, P.rcap), P.rcap, nm, add, nadd,
+                                    [&, pw = 0u](uint32_t kk) mutable {
+                                        if ((kk & 1u) == 0u) pw = ring_word(P.front, pid, kk >> 1, P.rcap);
+                                        return (pw >> ((kk & 1u) * 16u)) & 0xFFFFu;
+                                    });
+            publish_winner<N, V>(P, p, out, sb.z & 0xFFFFu, size, P.route != 0, c,
+                                 [&] { return MsgView{P.front, pid, P.rcap, nm, sb.w, sc.x, nadd, P.t.info}; });
         }
     }
 }
@@ -3792,58 +3858,16 @@ __global__ __launch_bounds__(XB_THREADS, (commit_items_waves<N, V, MR, MX, FUSE,
                 P.noff[out] = wd;
 #pragma unroll
                 for (int w = 0; w < CCW; w++) P.next[ring_wrap(rs + (uint32_t)w, P.rcap)] = pk[w];
-                // the parent's sorted ids (LDS) merged with the added ones (sorted here: BecomeCandidate
-                // adds its VoteReqs in peer order), written a word at a time, the last half-word padded
+                // the parent's ids from its record in LDS
                 uint32_t add[4] = {sb.w & 0xFFFFu, sb.w >> 16, sc.x & 0xFFFFu, sc.x >> 16};
-#pragma unroll
-                for (int x = 0; x < S::NADD; x++)
-#pragma unroll
-                    for (int y = 0; y + 1 < S::NADD - x; y++)
-                        if ((uint32_t)(y + 1) < nadd && add[y + 1] < add[y]) {
-                            const uint32_t t = add[y];
-                            add[y] = add[y + 1];
-                            add[y + 1] = t;
-                        }
                 const uint16_t *pid = reinterpret_cast<const uint16_t *>(rec + CCW);
-                const uint64_t oid = ring_wrap(rs + CCW, P.rcap);
-                uint32_t kk = 0, ai = 0, word = 0;
-                const uint32_t tot_ids = nm + nadd;
-                for (uint32_t o = 0; o < tot_ids; o++) {
-                    uint32_t next_add = 0xFFFFFFFFu;
-#pragma unroll
-                    for (int y = 0; y < S::NADD; y++) next_add = (uint32_t)y == ai ? add[y] : next_add;
-                    const uint32_t pv = kk < nm ? (uint32_t)pid[kk] : 0xFFFFFFFFu;
-                    uint32_t id;
-                    if (ai < nadd && next_add < pv) {
-                        id = next_add;
-                        ai++;
-                    } else {
-                        id = pv;
-                        kk++;
-                    }
-                    if (o & 1u) P.next[ring_wrap(oid + (o >> 1), P.rcap)] = word | (id << 16);
-                    else word = id;
-                }
-                if (tot_ids & 1u) P.next[ring_wrap(oid + (tot_ids >> 1), P.rcap)] = word;
-                const uint32_t key = sb.z & 0xFFFFu;
-                if (route) {
-                    // sharded round: the trace entry travels with the record to the state's next-level owner
-                    const uint64_t pref = P.gid_parent_base + p;
-                    P.xside[out] = make_uint4((uint32_t)pref, (uint32_t)(pref >> 32), key, size);
-                } else {
-                    const uint64_t gid = P.gid_next_base + out;
-                    P.par[gid - P.trace_base] = P.gid_parent_base + p;
-                    P.pslot[gid - P.trace_base] = (uint16_t)key;
-                }
-                int which = 0;
-                // (only NoAllCommit, tla:451-481, reads the message set: the ring's copy of the parent's ids)
-                const uint64_t mids = (P.inv_mask & 32u) ? ring_wrap(ring_wrap(P.fbase + P.foff[p], P.rcap) + CCW, P.rcap) : 0;
-                const MsgView mv{P.front, mids, P.rcap, nm, sb.w, sc.x, nadd, P.t.info};
-                const int iv = check_invs<N, V>(c, P.inv_order, &which, mv);
-                if (iv != 1 && !(iv == 0 && P.err[ERR_NSLOTS])) {
-                    const unsigned long long ek = ((((unsigned long long)p << 16) | key) << 8) | (unsigned long long)which;
-                    atomicMin(&P.err[iv == 0 ? ERR_INV : ERR_EVAL], ek);
-                }
+                merge_ids_lane<S::NADD>(P.next, ring_wrap(rs + CCW, P.rcap), P.rcap, nm, add, nadd,
+                                        [&](uint32_t kk) { return (uint32_t)pid[kk]; });
+                publish_winner<N, V>(P, p, out, sb.z & 0xFFFFu, size, route, c, [&] {
+                    // (only NoAllCommit, tla:451-481, reads the message set: the ring's copy of the parent's ids)
+                    const uint64_t mids = (P.inv_mask & 32u) ? ring_wrap(ring_wrap(P.fbase + P.foff[p], P.rcap) + CCW, P.rcap) : 0;
+                    return MsgView{P.front, mids, P.rcap, nm, sb.w, sc.x, nadd, P.t.info};
+                });
             }
             __syncthreads();
             if (tid == 0) sNW = 0u;
@@ -3964,45 +3988,13 @@ __global__ __launch_bounds__(64) void k_walk(KParams P, WalkParams Wp) {
             W.bm = sBM;
             Succ<N, V, MR> cand[NC];
             uint32_t akey = KEY_NONE;
-            int ln = lane;  // (opaque, as in k_expand: what the evaluation derives from it is not hoisted)
-            asm volatile("" : "+v"(ln));
-            uint32_t mid[MR], sid[N - 1];
-            {
-                uint32_t snat[N - 1];
-                slot_nats<N, V, MR>(P, W, ln, snat);
-#pragma unroll
-                for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
-#pragma unroll
-                for (int q = 0; q < N - 1; q++) sid[q] = nat_lookup(P, snat[q]);
-            }
-#pragma unroll
-            for (int r = 0; r < MR; r++)
-                eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey, nullptr, mid[r]);
-            eval_slot<N, V, MR>(P, W, ln, cand[MR], nullptr, sid);
-            // rank of every enabled successor in TLC order, and their number c
+            wave_eval<N, V, MR, BFV>(P, W, lane, cand, akey, nullptr);
+            // rank of every enabled successor in TLC order, and their number
             uint64_t en[NC];
-            uint32_t total = 0;
-#pragma unroll
-            for (int r = 0; r < NC; r++) {
-                en[r] = __ballot(cand[r].key != KEY_NONE);
-                total += (uint32_t)__popcll(en[r]);
-            }
+            const uint32_t total = wave_enabled<N, V, MR>(cand, en);
             uint32_t rank[NC];
-#pragma unroll
-            for (int r = 0; r < NC; r++) rank[r] = 0;
-#pragma unroll
-            for (int q = 0; q < NC; q++) {
-                for (uint64_t m = en[q]; m; m &= m - 1) {
-                    const int t = __ffsll((unsigned long long)m) - 1;
-                    const uint32_t kt = rdlane(cand[q].key, t);
-#pragma unroll
-                    for (int r = 0; r < NC; r++) rank[r] += kt < cand[r].key ? 1u : 0u;
-                }
-            }
-            bool ovf = false;
-#pragma unroll
-            for (int r = 0; r < NC; r++) ovf |= cand[r].key != KEY_NONE && W.nm + cand[r].nadd > (uint32_t)S::MCAP;
-            if (__ballot(ovf)) {  // the expansion's capacity rule: the call fails, the walk stops before any write
+            wave_ranks<N, V, MR>(cand, en, rank);
+            if (wave_overflow<N, V, MR>(W, cand)) {  // the call fails, the walk stops before any write
                 if (lane == 0) atomicMin(&Wp.err[1], (unsigned long long)i);
                 end = WALK_DROPPED;
                 break;
@@ -4011,18 +4003,9 @@ __global__ __launch_bounds__(64) void k_walk(KParams P, WalkParams Wp) {
             if (total == 0) { end = P.check_deadlock ? WALK_DEADLOCK : WALK_STUCK; break; }
             gen += total;
             const uint32_t idx = walk_choice(Wp.seed, walk, len - 1u, total);
-            // the one candidate of rank idx: each lane's own copy of it, then the lane that holds it
-            Succ<N, V, MR> ch = cand[MR];
-            bool hit = false;
-#pragma unroll
-            for (int r = 0; r < NC; r++) {
-                const bool h = cand[r].key != KEY_NONE && rank[r] == idx;
-                if (h) ch = cand[r];
-                hit |= h;
-            }
-            const uint64_t hm = __ballot(hit);
-            if (!hm) { end = WALK_DROPPED; break; }  // (unreachable: the ranks are a permutation of 0 .. c - 1)
-            const int t = __ffsll((unsigned long long)hm) - 1;
+            Succ<N, V, MR> ch;
+            const int t = wave_pick<N, V, MR>(cand, rank, idx, ch);
+            if (t < 0) { end = WALK_DROPPED; break; }
             const uint32_t key = rdlane(ch.key, t);
             if (lane == 0) Wp.keys[(uint64_t)i * dm1 + (len - 1u)] = (uint16_t)key;
             len++;
@@ -4058,7 +4041,7 @@ __global__ __launch_bounds__(64) void k_walk(KParams P, WalkParams Wp) {
 // ---- action coverage (rmc_set_coverage; TLC's -coverage) -------------------------------------------
 // The successors each action of Next generates, counted on the side of the BFS: a 64-lane wave per
 // parent, grid-strided over the chunk's frontier records.  A parent is loaded and its candidates are
-// evaluated exactly as k_expand and k_walk do -- and that is all: no ranks, no records, no fingerprints,
+// evaluated (load_parent, wave_eval) -- and that is all: no ranks, no records, no fingerprints,
 // no seen set.  What TLC's "states generated" counts is every enabled candidate, self-loops and repeats
 // included, so per action the wave adds the popcount of the ballot of lanes whose candidate is enabled
 // and carries that action in its slot key.  The counters are wave-uniform and stay in registers across
@@ -4093,21 +4076,7 @@ __global__ __launch_bounds__(64) void k_cover(KParams P, CoverParams Cp) {
         W.bm = sBM;
         Succ<N, V, MR> cand[NC];
         uint32_t akey = KEY_NONE;
-        int ln = lane;  // (opaque, as in k_expand: what the evaluation derives from it is not hoisted)
-        asm volatile("" : "+v"(ln));
-        uint32_t mid[MR], sid[N - 1];
-        {
-            uint32_t snat[N - 1];
-            slot_nats<N, V, MR>(P, W, ln, snat);
-#pragma unroll
-            for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
-#pragma unroll
-            for (int q = 0; q < N - 1; q++) sid[q] = nat_lookup(P, snat[q]);
-        }
-#pragma unroll
-        for (int r = 0; r < MR; r++)
-            eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey, nullptr, mid[r]);
-        eval_slot<N, V, MR>(P, W, ln, cand[MR], nullptr, sid);
+        wave_eval<N, V, MR, BFV>(P, W, lane, cand, akey, nullptr);
 #pragma unroll
         for (int r = 0; r < NC; r++) {
             const uint32_t k = cand[r].key;
@@ -4247,9 +4216,9 @@ __global__ __launch_bounds__(64) void k_gid_insert(KParams P, uint64_t n, GidMap
     }
 }
 
-// The edges of the parents of a launch, a 64-lane wave per parent, grid-strided.  A parent is loaded and its
-// candidates are evaluated exactly as k_expand, k_walk and k_cover do, and ranked in TLC order as k_expand's
-// M_SINGLE mode ranks them for rmc_successors.  Count pass (Ep.off == nullptr): the parent's number of edges
+// The edges of the parents of a launch, a 64-lane wave per parent, grid-strided.  A parent is loaded, its
+// candidates are evaluated (wave_eval) and ranked in TLC order (wave_enabled, wave_ranks: the order of
+// rmc_successors).  Count pass (Ep.off == nullptr): the parent's number of edges
 // under the cut.  Write pass: each successor in rank order is rebuilt as a record in LDS (write_record, as
 // k_walk does) and fingerprinted as a whole state (k_fp_states' device code) unless it is its parent bit for
 // bit; then the lanes look the parent's fingerprints up in the gid map together -- one random 32-B read each
@@ -4287,71 +4256,33 @@ __global__ __launch_bounds__(64) void k_edges(KParams P, EdgeParams Ep) {
         W.bm = sBM;
         Succ<N, V, MR> cand[NC];
         uint32_t akey = KEY_NONE;
-        int ln = lane;  // (opaque, as in k_expand: what the evaluation derives from it is not hoisted)
-        asm volatile("" : "+v"(ln));
-        uint32_t mid[MR], sid[N - 1];
-        {
-            uint32_t snat[N - 1];
-            slot_nats<N, V, MR>(P, W, ln, snat);
-#pragma unroll
-            for (int r = 0; r < MR; r++) mid[r] = nat_lookup(P, msg_nat<N, V, MR>(P, W, r, ln));
-#pragma unroll
-            for (int q = 0; q < N - 1; q++) sid[q] = nat_lookup(P, snat[q]);
-        }
-#pragma unroll
-        for (int r = 0; r < MR; r++)
-            eval_msg<N, V, MR, BFV>(P, W, r, ln, cand[r], cand[BFV ? MR + 1 + r : r], akey, nullptr, mid[r]);
-        eval_slot<N, V, MR>(P, W, ln, cand[MR], nullptr, sid);
+        wave_eval<N, V, MR, BFV>(P, W, lane, cand, akey, nullptr);
         // the cut takes a prefix of TLC's order: the ranks of what stays are those of the whole list
-        uint64_t en[NC];
-        uint32_t total = 0;
 #pragma unroll
-        for (int r = 0; r < NC; r++) {
+        for (int r = 0; r < NC; r++)
             if (cand[r].key >= klim) cand[r].key = KEY_NONE;
-            en[r] = __ballot(cand[r].key != KEY_NONE);
-            total += (uint32_t)__popcll(en[r]);
-        }
+        uint64_t en[NC];
+        uint32_t total = wave_enabled<N, V, MR>(cand, en);
         if (!Ep.off) {
             if (lane == 0) Ep.cnt[pl] = total;
             __syncthreads();  // the bitmap and the core in LDS are read out before the next parent's go in
             continue;
         }
         uint32_t rank[NC];
-#pragma unroll
-        for (int r = 0; r < NC; r++) rank[r] = 0;
-#pragma unroll
-        for (int q = 0; q < NC; q++) {
-            for (uint64_t m = en[q]; m; m &= m - 1) {
-                const int t = __ffsll((unsigned long long)m) - 1;
-                const uint32_t kt = rdlane(cand[q].key, t);
-#pragma unroll
-                for (int r = 0; r < NC; r++) rank[r] += kt < cand[r].key ? 1u : 0u;
-            }
-        }
-        bool ovf = false;  // (the search stopped with RMC_E_CAPACITY before such a parent's level was committed)
-#pragma unroll
-        for (int r = 0; r < NC; r++) ovf |= cand[r].key != KEY_NONE && W.nm + cand[r].nadd > (uint32_t)S::MCAP;
-        if (__ballot(ovf) || total > (uint32_t)MX) {
+        wave_ranks<N, V, MR>(cand, en, rank);
+        // (the search stopped with RMC_E_CAPACITY before such a parent's level was committed)
+        if (wave_overflow<N, V, MR>(W, cand) || total > (uint32_t)MX) {
             if (lane == 0) atomicOr(Ep.flag, 2u);
             total = 0;
         }
         for (uint32_t idx = 0; idx < total; idx++) {
-            // the one candidate of rank idx: each lane's own copy of it, then the lane that holds it
-            Succ<N, V, MR> ch = cand[MR];
-            bool hit = false;
-#pragma unroll
-            for (int r = 0; r < NC; r++) {
-                const bool h = cand[r].key != KEY_NONE && rank[r] == idx;
-                if (h) ch = cand[r];
-                hit |= h;
-            }
-            const uint64_t hm = __ballot(hit);
-            if (!hm) {  // (unreachable: the ranks are a permutation of 0 .. total - 1)
+            Succ<N, V, MR> ch;
+            const int t = wave_pick<N, V, MR>(cand, rank, idx, ch);
+            if (t < 0) {
                 if (lane == 0) atomicOr(Ep.flag, 2u);
                 if (lane == 0) sKey[idx] = 1u << 16;
                 continue;
             }
-            const int t = __ffsll((unsigned long long)hm) - 1;
             const uint32_t key = rdlane(ch.key, t);
             const bool self = rdlane(ch.self ? 1u : 0u, t) != 0u;
             if (lane == 0) sKey[idx] = key | (self ? 1u << 16 : 0u);
@@ -4383,10 +4314,10 @@ __global__ __launch_bounds__(64) void k_edges(KParams P, EdgeParams Ep) {
     }
 }
 
-static inline unsigned grid_for(uint64_t n) {
-    const uint64_t cap = 256ull * RMC_GRID_PER_CU;  // one-wave blocks per CU (default 32) on 256 CUs
-    return (unsigned)(n < cap ? (n ? n : 1) : cap);
-}
+// a grid of n blocks: one at least, cap at most (the kernels stride over what is left)
+static inline unsigned clamp_grid(uint64_t n, uint64_t cap) { return (unsigned)(n < cap ? (n ? n : 1) : cap); }
+// one-wave blocks per CU (default 32) on 256 CUs
+static inline unsigned grid_for(uint64_t n) { return clamp_grid(n, 256ull * RMC_GRID_PER_CU); }
 
 // Blocks of `threads` threads of a kernel that a CU keeps resident: the runtime's answer, cut to what the
 // hardware admits -- at most 8 waves per SIMD, and at most 800 / (SGPRs rounded up to 16, + 16) of them; the
@@ -4415,7 +4346,7 @@ struct Launch {
     static void fused(const KParams &P, hipStream_t s) {
         if (!P.route) {  // a block per XF_PARENTS parents, fingerprints and election in the same launch
             const uint64_t nbat = (P.p_end - P.p_begin + XF_PARENTS - 1) / XF_PARENTS;
-            hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, true, XF_PARENTS>), dim3((unsigned)(nbat < 8192 ? (nbat ? nbat : 1) : 8192)),
+            hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, true, XF_PARENTS>), dim3(clamp_grid(nbat, 8192)),
                                dim3(XB_THREADS), 0, s, P);
             return;
         }
@@ -4434,8 +4365,7 @@ struct Launch {
         hipLaunchKernelGGL(k, dim3(items_grid(nbat, grid)), dim3(items_threads<N, V, MR, false>()), 0, s, P);
     }
     static unsigned items_grid(uint64_t nbat, unsigned grid) {
-        const uint64_t cap = grid ? grid : 2048u;
-        return (unsigned)(nbat < cap ? (nbat ? nbat : 1) : cap);
+        return clamp_grid(nbat, grid ? grid : 2048u);
     }
     // blocks per CU of the split expansion and of the split items commit (0: k_commit_split commits)
     static hipError_t items_blocks(int *expand, int *commit) {
@@ -4458,12 +4388,12 @@ struct Launch {
         Q.prun = P.route ? 1u : P.prun ? P.prun : (uint32_t)(fit < 1 ? 1 : fit < (uint64_t)PROBE_RUN ? fit : (uint64_t)PROBE_RUN);
         const uint64_t per = 256ull * Q.prun;
         const uint64_t blocks = (np + per - 1) / per;
-        hipLaunchKernelGGL((k_hash_probe<N, V, MR, MX>), dim3(blocks ? (unsigned)(blocks < 16384ull ? blocks : 16384ull) : 1u),
+        hipLaunchKernelGGL((k_hash_probe<N, V, MR, MX>), dim3(clamp_grid(blocks, 16384)),
                            dim3(256), 0, s, Q);
     }
     static void insert(const KParams &P, uint64_t np, hipStream_t s) {
         const uint64_t blocks = (np + 255) / 256;
-        hipLaunchKernelGGL((k_insert_winners<MX>), dim3(blocks ? (unsigned)(blocks < 16384ull ? blocks : 16384ull) : 1u),
+        hipLaunchKernelGGL((k_insert_winners<MX>), dim3(clamp_grid(blocks, 16384)),
                            dim3(256), 0, s, P);
     }
     static void wincount(const KParams &P, uint64_t np, hipStream_t s) {
@@ -4475,7 +4405,7 @@ struct Launch {
             if (!P.route && !P.split && !P.plist) {  // a block per 16 parents, records in LDS
                 const uint64_t nbat = (P.p_end - P.p_begin + XC_PARENTS - 1) / XC_PARENTS;
                 hipLaunchKernelGGL((k_commit_items<N, V, MR, MX, true, XC_PARENTS>),
-                                   dim3((unsigned)(nbat < 8192 ? (nbat ? nbat : 1) : 8192)), dim3(XB_THREADS), 0, s, P);
+                                   dim3(clamp_grid(nbat, 8192)), dim3(XB_THREADS), 0, s, P);
                 return;
             }
         }
@@ -4496,21 +4426,21 @@ struct Launch {
                 return;
             }
         }
-        hipLaunchKernelGGL((k_commit_split<N, V, MR, MX>), dim3(blocks ? (unsigned)(blocks < 16384ull ? blocks : 16384ull) : 1u),
+        hipLaunchKernelGGL((k_commit_split<N, V, MR, MX>), dim3(clamp_grid(blocks, 16384)),
                            dim3(256), 0, s, P);
         hipLaunchKernelGGL((k_commit_finish<MX, Spec<N, V, MR>::RECW_MAX>), dim3(1), dim3(64), 0, s, P);
     }
     static void local_elect(const KParams &P, uint64_t np, Seen seen, ESlot *OT,
                             uint64_t mask, uint32_t round, uint32_t W, uint32_t self, uint64_t g0, hipStream_t s) {
         const uint64_t blocks = (np + 255) / 256;  // a wave per 64 parents (each_successor)
-        hipLaunchKernelGGL((k_local_elect<MX, Spec<N, V, MR>::SW4>), dim3(blocks ? (unsigned)(blocks < 16384ull ? blocks : 16384ull) : 1u),
+        hipLaunchKernelGGL((k_local_elect<MX, Spec<N, V, MR>::SW4>), dim3(clamp_grid(blocks, 16384)),
                            dim3(256), 0, s, P, seen, OT, mask, round, W, self, g0);
     }
     static void local_flags(const KParams &P, uint64_t np, Seen seen, const ESlot *OT, uint32_t round,
                             uint32_t W, uint32_t self, uint64_t g0, unsigned long long *inserted, hipStream_t s) {
         const uint64_t blocks = (np + 255) / 256;
         hipLaunchKernelGGL((k_local_flags<MX>),
-                           dim3(blocks ? (unsigned)(blocks < 16384ull ? blocks : 16384ull) : 1u), dim3(256), 0, s, P,
+                           dim3(clamp_grid(blocks, 16384)), dim3(256), 0, s, P,
                            seen, OT, round, W, self, g0, inserted);
     }
     static void walk(const KParams &P, const WalkParams &wp, hipStream_t s) {
@@ -4521,7 +4451,7 @@ struct Launch {
     }
     static void viol(const KParams &P, uint64_t n, const ViolParams &vp, hipStream_t s) {
         const uint64_t b = (n + 255) / 256;
-        if (n) hipLaunchKernelGGL((k_viol_scan<N, V, MR>), dim3((unsigned)(b < 4096 ? b : 4096)), dim3(256), 0, s, P, n, vp);
+        if (n) hipLaunchKernelGGL((k_viol_scan<N, V, MR>), dim3(clamp_grid(b, 4096)), dim3(256), 0, s, P, n, vp);
     }
     static void gid_insert(const KParams &P, uint64_t n, GidMap g, uint64_t gid0, hipStream_t s) {
         if (n) hipLaunchKernelGGL((k_gid_insert<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n, g, gid0);
@@ -4537,7 +4467,7 @@ struct Launch {
     }
     static void inv_values(const KParams &P, uint64_t n, uint16_t *out, hipStream_t s) {
         const uint64_t b = (n + 255) / 256;
-        if (n) hipLaunchKernelGGL((k_inv_values<N, V, MR>), dim3((unsigned)(b < 4096 ? b : 4096)), dim3(256), 0, s, P, n, out);
+        if (n) hipLaunchKernelGGL((k_inv_values<N, V, MR>), dim3(clamp_grid(b, 4096)), dim3(256), 0, s, P, n, out);
     }
     static void enc(const uint32_t *c, uint32_t *o) { encode_core<N, V>(c, o); }
     static void dec(const uint32_t *w, uint32_t *c) { decode_core<N, V>(w, c); }
