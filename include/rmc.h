@@ -70,7 +70,8 @@ extern "C" {
 
 /* Model configuration: what Raft.cfg's CONSTANTS (Raft.cfg:1-21), INVARIANT
  * (Raft.cfg:33-34) and TLC's -deadlock flag (myrun.sh:3) bind.  VIEW view
- * (Raft.cfg:26) is always on; SYMMETRY symmServers (Raft.cfg:24) unless
+ * (Raft.cfg:26) is on unless rmc_set_full_state turns it off (below: the whole
+ * state is then the identity); SYMMETRY symmServers (Raft.cfg:24) unless
  * no_symmetry.  A zero-initialised struct plus the four constants and
  * invariants = RMC_INV_LEADER_HAS_ALL_COMMITTED is Raft.cfg under myrun.sh.
  *
@@ -343,6 +344,22 @@ typedef struct rmc_coverage {
 } rmc_coverage;
 int rmc_set_coverage(void *ctx, int on);
 int rmc_get_coverage(void *ctx, rmc_coverage *out);
+
+/* The whole state as the identity.  By default a state is identified by the cfg's VIEW (Raft.tla:38), which
+ * leaves out electionCount, restartCount, pendingResponse and valSent although each guards an action
+ * (Raft.tla:108, :411, :246 / :380, :236): two states that differ only there are one "distinct state", and the
+ * one found first stands for both, successors included.  With this setting on, the 128-bit fingerprint is
+ * a function of all twelve variables -- under SYMMETRY the minimum over the same coset of server
+ * permutations, pendingResponse permuted on both indices -- so a "distinct state" is a SYMMETRY class of
+ * whole states (a whole state without SYMMETRY) and the search no longer depends on which member of a VIEW
+ * class is met first.  Everything that works on fingerprints follows: the seen set, the sharded owners,
+ * coverage's distinct counts, continuation, graph mode and the kept graph's queries, rmc_fingerprint(s) and
+ * rmc_seen_contains.  rmc_simulate keeps no seen set and is not affected.
+ * rmc_set_full_state: after rmc_create or rmc_reset and before rmc_init / rmc_init_from / rmc_resume
+ * (RMC_E_STATE once a search holds states); rmc_reset keeps the setting; every rank of a sharded run sets
+ * it.  A checkpoint stores it: rmc_resume under the other setting fails with "not a checkpoint of this
+ * configuration" (checkpoints written before the setting existed are VIEW checkpoints).  Off by default. */
+int rmc_set_full_state(void *ctx, int on);
 
 /* Continuation (TLC's -continue): search past invariant violations and count them per invariant.
  * With it on, a new state on which an invariant evaluates to FALSE no longer ends the search: it is

@@ -220,7 +220,7 @@ bool parse_model(const std::string &cfg_text, const char *tla_text, ParsedModel 
         i++;
     }
     if (!have_init || !have_next) { err = "cfg must name INIT Init and NEXT Next (Raft.cfg:30-31)"; return false; }
-    if (!pm->view) { err = "cfg must select VIEW view (Raft.cfg:26): only the VIEW configuration is compiled"; return false; }
+    if (!pm->view) { err = "cfg must select VIEW view (Raft.cfg:26): only the VIEW configuration is compiled: keep the line (to search on the whole state instead, keep it and pass raftmc -fullstate / call rmc_set_full_state)"; return false; }
     auto need_int = [&](const char *n, int32_t *dst, int lo, int hi) {
         auto it = consts.find(n);
         if (it == consts.end() || it->second.kind != Value::INT) { err = std::string("CONSTANT ") + n + " must be an integer"; return false; }

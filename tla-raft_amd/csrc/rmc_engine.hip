@@ -573,6 +573,9 @@ struct rmc_ctx {
     // before the host could count it.
     static constexpr int COV_N = 32;  // generated[16], distinct[16]
     bool coverage = false;
+    // rmc_set_full_state: the fingerprint covers all twelve variables, not the cfg's VIEW (KParams::full).
+    // Kept over rmc_reset; stored in a checkpoint's header and mixed into its scheme word.
+    bool full_state = false;
     uint64_t cov_total[COV_N] = {0};  // the run's totals without Init, global on every rank
     uint64_t cov_level[COV_N] = {0};  // sharded: the current level's rounds so far
     void cov_alloc() {
@@ -939,6 +942,7 @@ struct rmc_ctx {
         P.t.seeds = d_seeds;
         P.t.np = np;
         P.t.bmw = (uint32_t)((U.info.size() + 31) / 32);
+        P.full = full_state ? 1u : 0u;
         P.seen = s.seen();
         P.rcap = ~0ull;  // fixed-stride buffers unless a ring is set
         P.err = s.err;
@@ -4246,7 +4250,9 @@ struct rmc_ctx {
         h.inv_order = inv_order;
         h.check_deadlock = cfg.check_deadlock; h.spec_variant = cfg.spec_variant;
         h.no_symmetry = cfg.no_symmetry; h.msg_cap = ks.MCAP;
-        h.scheme = scheme_hash;
+        // (pad0 = 0, the scheme word as it was: a checkpoint written before the setting existed is a VIEW one)
+        h.pad0 = full_state ? 1 : 0;
+        h.scheme = full_state ? mix64(scheme_hash ^ 0x66756c6c73746174ull) : scheme_hash;
         h.W = multi ? W : 0;
         h.first_shard = multi ? sh[0].id : 0;
         h.nshards = (int32_t)sh.size();
@@ -4404,7 +4410,8 @@ struct rmc_ctx {
         if (!ok || h.magic != CKPT_MAGIC || h.abi != want.abi || h.recw != want.recw || h.n != want.n ||
             h.v != want.v || h.e != want.e || h.r != want.r || h.invariants != want.invariants ||
             h.inv_order != want.inv_order || h.check_deadlock != want.check_deadlock ||
-            h.spec_variant != want.spec_variant || h.no_symmetry != want.no_symmetry || h.msg_cap != want.msg_cap)
+            h.spec_variant != want.spec_variant || h.no_symmetry != want.no_symmetry || h.msg_cap != want.msg_cap ||
+            h.pad0 != want.pad0)
             fail(" is not a checkpoint of this configuration");
         if (h.scheme != want.scheme) fail(" was written with another fingerprint scheme");
         // A sharded checkpoint written with a SMALLER chunk size than this context's is adopted (the chunk
@@ -4762,6 +4769,15 @@ int rmc_set_coverage(void *ctx, int on) {
     return guarded(c, [&] {
         if (c->inited) throw Fail(RMC_E_STATE, "rmc_set_coverage: after rmc_create or rmc_reset, before rmc_init");
         c->coverage = on != 0;
+        return RMC_OK;
+    });
+}
+
+int rmc_set_full_state(void *ctx, int on) {
+    rmc_ctx *c = (rmc_ctx *)ctx;
+    return guarded(c, [&] {
+        if (c->inited) throw Fail(RMC_E_STATE, "rmc_set_full_state: after rmc_create or rmc_reset, before rmc_init");
+        c->full_state = on != 0;
         return RMC_OK;
     });
 }

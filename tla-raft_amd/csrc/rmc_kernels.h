@@ -155,6 +155,10 @@ struct KParams {
     // takes lslot == LS_WIN as the verdict and writes each winner's trace entry to its sidecar
     // xside[i] = {parent global id lo, hi, slot key, record words} instead of par / pslot
     int route;
+    // rmc_set_full_state: non-zero = the fingerprint covers the whole state, 0 = the cfg's VIEW.  Read by the launch
+    // wrappers only, which pick each fingerprinting kernel's FULL instantiation.  (Here it fills what was padding
+    // before the pointer below: no other field moves, so a VIEW kernel reads its arguments where it always did.)
+    uint32_t full;
     uint4 *xside;
     uint32_t *ocnt;            // sharded split round: k_hash_probe counts the successors per owner here
     uint32_t nown;             // ... of that many owners (W)

@@ -508,35 +508,57 @@ __device__ __forceinline__ bool lex_less(ulonglong2 a, ulonglong2 b) {  // (h1, 
 }
 
 // Per-server and per-pair inputs of the content matrix, from the words of one row.
+// prow: the server's pendingResponse row (bit j: pendingResponse[i][j]) under the whole-state identity
+// (a kernel's FULL, picked at launch from KParams::full), 0 under the VIEW, which leaves the variable out (Raft.tla:38).
 template <int N>
 __device__ __forceinline__ uint64_t own_word(uint32_t vfw, uint32_t ctw, uint32_t rolew, uint32_t ciw, uint32_t llw,
-                                             uint32_t lw, uint32_t mirow, uint32_t nirow, uint32_t i) {
+                                             uint32_t lw, uint32_t mirow, uint32_t nirow, uint32_t i, uint32_t prow) {
     const uint32_t vf = nib(vfw, i);
     const uint32_t vrel = vf == VF_NONE ? 0u : (vf == i ? 1u : 2u);
     const uint32_t own = vrel | (nib(ctw, i) << 2) | (nib(rolew, i) << 6) | (nib(ciw, i) << 10) |
-                         (nib(llw, i) << 14) | (nib(mirow, i) << 18) | (nib(nirow, i) << 22);
+                         (nib(llw, i) << 14) | (nib(mirow, i) << 18) | (nib(nirow, i) << 22) |
+                         (((prow >> i) & 1u) << 26);
     return ((uint64_t)lw << 32) | own;
 }
-__device__ __forceinline__ uint64_t pair_small(uint32_t mirow, uint32_t nirow, uint32_t vf_i, uint32_t j) {
-    return (uint64_t)(nib(mirow, j) | (nib(nirow, j) << 4) | ((vf_i == j) ? 256u : 0u));
+__device__ __forceinline__ uint64_t pair_small(uint32_t mirow, uint32_t nirow, uint32_t vf_i, uint32_t j, uint32_t prow) {
+    return (uint64_t)(nib(mirow, j) | (nib(nirow, j) << 4) | ((vf_i == j) ? 256u : 0u) | (((prow >> j) & 1u) << 9));
+}
+// server t's pendingResponse row of a core, masked by the setting (full: 0 or ~0u)
+template <int N>
+__device__ __forceinline__ uint32_t pend_row(const uint32_t *c, uint32_t t, uint32_t full) {
+    return ((c[Layout<N, 1>::W_PEND] & full) >> (t * N)) & ((1u << N) - 1u);
+}
+// The variables that name no server -- electionCount, restartCount, valSent (W_MISC bits [11:0]; |msgs|
+// above them follows from the message hashes) -- as one permutation-invariant term per half, combined
+// with the coset minimum.  Zero under the VIEW: the fingerprint is then what it was without the setting.
+constexpr uint32_t MISC_HIDDEN = 0xFFFu;
+constexpr uint64_t CK_G0 = 0x51afd7ed558ccd6dULL, CK_G1 = 0xc4ceb9fe1a85ec53ULL;
+__device__ __forceinline__ ulonglong2 with_global(ulonglong2 best, uint32_t misc, uint32_t full) {
+    if (full) {
+        const uint64_t g = (uint64_t)(misc & MISC_HIDDEN);
+        best.x ^= mix64(g * PAIR_K0 + CK_G0);
+        best.y ^= mix64(g * PAIR_K1 + CK_G1);
+    }
+    return make_ulonglong2(best.x | 1ull, best.y);
 }
 // content C_f[t][j] of row t from its words and its message-hash sums toward j (Ms0/Ms1)
 template <int N>
 __device__ __forceinline__ uint64_t content(int f, uint32_t t, uint32_t j, const uint32_t *c, uint32_t lw_t,
-                                            uint32_t mirow, uint32_t nirow, uint64_t Ms) {
+                                            uint32_t mirow, uint32_t nirow, uint64_t Ms, uint32_t full) {
     using Lo = Layout<N, 1>;
+    const uint32_t prow = pend_row<N>(c, t, full);
     if (t == j)
         return cmix_own(own_word<N>(c[Lo::W_VF], c[Lo::W_CT], c[Lo::W_ROLE], c[Lo::W_CI], c[Lo::W_LL], lw_t, mirow,
-                                    nirow, t),
+                                    nirow, t, prow),
                         f);
-    const uint64_t sm = pair_small(mirow, nirow, nib(c[Lo::W_VF], t), j);
+    const uint64_t sm = pair_small(mirow, nirow, nib(c[Lo::W_VF], t), j, prow);
     return cmix_pair(Ms ^ (sm * (f ? PAIR_K1 : PAIR_K0)), f);
 }
 
 // The fingerprint of a whole state: nibble core c, message-hash sums M_f[t * N + j] (src t, dst j).
 template <int N, int V>
 __device__ __forceinline__ ulonglong2 fingerprint(const uint32_t *c, const uint64_t *M0, const uint64_t *M1,
-                                                  const Tables &t) {
+                                                  const Tables &t, const uint32_t full) {
     using Lo = Layout<N, V>;
     uint64_t C0[N * N], C1[N * N], sig[N];
 #pragma unroll
@@ -544,8 +566,8 @@ __device__ __forceinline__ ulonglong2 fingerprint(const uint32_t *c, const uint6
         sig[i] = 0;
 #pragma unroll
         for (int j = 0; j < N; j++) {
-            C0[i * N + j] = content<N>(0, i, j, c, c[Lo::W_LOG + i], c[Lo::W_MI + i], c[Lo::W_NI + i], M0[i * N + j]);
-            C1[i * N + j] = content<N>(1, i, j, c, c[Lo::W_LOG + i], c[Lo::W_MI + i], c[Lo::W_NI + i], M1[i * N + j]);
+            C0[i * N + j] = content<N>(0, i, j, c, c[Lo::W_LOG + i], c[Lo::W_MI + i], c[Lo::W_NI + i], M0[i * N + j], full);
+            C1[i * N + j] = content<N>(1, i, j, c, c[Lo::W_LOG + i], c[Lo::W_MI + i], c[Lo::W_NI + i], M1[i * N + j], full);
             sig[i] += C1[i * N + j];
         }
     }
@@ -557,7 +579,7 @@ __device__ __forceinline__ ulonglong2 fingerprint(const uint32_t *c, const uint6
             [&](int f, uint32_t a, uint32_t b) { return t.seeds[f * SEEDS_PER_F + a * MAXN + b]; });
         if (lex_less(h, best)) best = h;
     }
-    return make_ulonglong2(best.x | 1ull, best.y);
+    return with_global(best, c[Lo::W_MISC], full);
 }
 constexpr int factorial(int n) { return n <= 1 ? 1 : n * factorial(n - 1); }
 
@@ -1393,10 +1415,12 @@ __device__ __forceinline__ uint64_t msg_hash_half(uint32_t info, int f) {
 // A staged successor's fingerprint (rmc_spec.h): its content matrix rebuilt from the parent's decoded
 // core pc, the parent's message-hash sums per server pair (mp(pi) = {M_0, M_1} of pair pi) and the
 // staged row (sa, sb, sc: the acting server's row and the added messages), then the coset minimum
-// (ai(a, id): the info word of added message a, id its message id)
+// (ai(a, id): the info word of added message a, id its message id; full: the calling kernel's FULL as a mask,
+// a constant, so that a VIEW instantiation is the code it was before the setting existed)
 template <int N, int V, int MR, class FM, class FA>
 __device__ __forceinline__ ulonglong2 staged_fp(const KParams &P, const uint32_t *pc, FM mp, FA ai, const uint4 sa,
-                                                const uint4 sb, const uint4 sc, const uint64_t (*sK)[N * N]) {
+                                                const uint4 sb, const uint4 sc, const uint64_t (*sK)[N * N],
+                                                const uint32_t full) {
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
     uint32_t c[Lo::NW];
@@ -1432,8 +1456,8 @@ __device__ __forceinline__ ulonglong2 staged_fp(const KParams &P, const uint32_t
                 m0 = m.x + ((uint32_t)t == sv ? ad0[j] : 0ull);
                 m1 = m.y + ((uint32_t)t == sv ? ad1[j] : 0ull);
             }
-            C0[t * N + j] = content<N>(0, t, j, c, c[Lo::W_LOG + t], c[Lo::W_MI + t], c[Lo::W_NI + t], m0);
-            C1[t * N + j] = content<N>(1, t, j, c, c[Lo::W_LOG + t], c[Lo::W_MI + t], c[Lo::W_NI + t], m1);
+            C0[t * N + j] = content<N>(0, t, j, c, c[Lo::W_LOG + t], c[Lo::W_MI + t], c[Lo::W_NI + t], m0, full);
+            C1[t * N + j] = content<N>(1, t, j, c, c[Lo::W_LOG + t], c[Lo::W_MI + t], c[Lo::W_NI + t], m1, full);
             sig[t] += C1[t * N + j];
         }
     }
@@ -1445,7 +1469,7 @@ __device__ __forceinline__ ulonglong2 staged_fp(const KParams &P, const uint32_t
             [&](int f, uint32_t a, uint32_t b) { return sK[f][a * N + b]; });
         if (lex_less(h, best)) best = h;
     }
-    return make_ulonglong2(best.x | 1ull, best.y);
+    return with_global(best, c[Lo::W_MISC], full);
 }
 
 // The fused election of a new fingerprint (the seen set is read-only in the launch): its slot q's
@@ -1560,7 +1584,7 @@ constexpr int expand_waves() {
 
 // BFV: the BecomeFollower variant (tla:420) -- MR more candidates (one per message lane) and MR * 64
 // more successor slots per parent (MX)
-template <int N, int V, int MR, int MODE, bool BFV = false>
+template <int N, int V, int MR, int MODE, bool BFV, bool FULL>  // FULL: rmc_set_full_state, as k_hash_probe (no default: a launch names it)
 __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expand(KParams P) {
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
@@ -1688,7 +1712,7 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
         if (lane < 2 * N * N) {
             const int f = lane / (N * N), t = (lane / N) % N, j = lane % N;
             pC[f][t * N + j] = content<N>(f, (uint32_t)t, (uint32_t)j, W.c, pcore[Lo::W_LOG + t], pcore[Lo::W_MI + t],
-                                          pcore[Lo::W_NI + t], f ? M1[t * N + j] : M0[t * N + j]);
+                                          pcore[Lo::W_NI + t], f ? M1[t * N + j] : M0[t * N + j], FULL ? ~0u : 0u);
         }
         // (b) every enabled successor's row inputs at its TLC rank
 #pragma unroll
@@ -1696,11 +1720,12 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
             if (cand[r].key == KEY_NONE) continue;
             const Succ<N, V, MR> &o = cand[r];
             const uint32_t g = rank[r];
-            const uint32_t vfs = nib(o.c[Lo::W_VF], o.s);
+            const uint32_t vfs = nib(o.c[Lo::W_VF], o.s), prow = pend_row<N>(o.c, o.s, FULL ? ~0u : 0u);
             sUg[g] = own_word<N>(o.c[Lo::W_VF], o.c[Lo::W_CT], o.c[Lo::W_ROLE], o.c[Lo::W_CI], o.c[Lo::W_LL], o.lw,
-                                 o.mirow, o.nirow, o.s);
-            sW1[g] = o.mirow | (vfs << 20);  // rows of N <= 5 nibbles
-            sW2[g] = o.nirow;
+                                 o.mirow, o.nirow, o.s, prow);
+            // rows of N <= 5 nibbles; a FULL kernel adds the pendingResponse row and with_global's input
+            sW1[g] = o.mirow | (vfs << 20) | (FULL ? prow << 24 : 0u);
+            sW2[g] = o.nirow | (FULL ? (o.c[Lo::W_MISC] & MISC_HIDDEN) << 20 : 0u);
             // (BecomeFollower candidates, r > MR, add no messages: their info words are never read)
             sCa[g] = (uint16_t)(((r <= MR ? r : 0) * 64 + lane) * S::NADD);
             sS[g] = (uint8_t)o.s;
@@ -1715,7 +1740,7 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
         }
         PHASE(4);
         auto emit = [&](uint32_t lo, ulonglong2 best) {
-            const ulonglong2 f = make_ulonglong2(best.x | 1ull, best.y);
+            const ulonglong2 f = with_global(best, sW2[lo] >> 20, FULL ? ~0u : 0u);
             if (MODE == M_FUSED) {
                 P.fp[pl * (uint64_t)MX + lo] = f;  // sharded round: the fingerprint's owner probes and elects
             } else {
@@ -1729,7 +1754,8 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
                 const uint32_t l = (uint32_t)lane % HB, g = b0 + l;
                 if (l < nb) {
                     const uint32_t sv = sS[g], w1 = sW1[g], na = sNa[g];
-                    const uint32_t mirow = w1 & 0xFFFFFu, vfs = w1 >> 20, nirow = sW2[g];
+                    const uint32_t mirow = w1 & 0xFFFFFu, vfs = FULL ? (w1 >> 20) & 15u : w1 >> 20, prow = FULL ? w1 >> 24 : 0u;
+                    const uint32_t nirow = FULL ? sW2[g] & 0xFFFFFu : sW2[g];
                     const uint64_t u = sUg[g];
                     const uint32_t *ai = &sAinf[sCa[g]];
 #pragma unroll
@@ -1751,7 +1777,7 @@ __global__ __launch_bounds__(64, (expand_waves<N, MR, MODE, BFV>())) void k_expa
 #pragma unroll
                         for (int j = 0; j < N; j++) {
                             if ((uint32_t)j == sv) continue;
-                            const uint64_t sm = pair_small(mirow, nirow, vfs, (uint32_t)j);
+                            const uint64_t sm = pair_small(mirow, nirow, vfs, (uint32_t)j, prow);
                             sC[f][l * N + j] = cmix_pair(row[j] ^ (sm * (f ? PAIR_K1 : PAIR_K0)), f);
                         }
                     }
@@ -2252,8 +2278,9 @@ __device__ __forceinline__ uint32_t slot_class(uint32_t t) {
 // (the fused BecomeFollower kernel is not cut to RMC_FUSED_WAVES: at 4 waves per SIMD it spills 23 VGPRs, and with
 // the message-parent notes that build gave wrong BecomeFollower n3 counts while the uncut one matches the oracle --
 // profiles/r06_ab_message_parents.txt)
-template <int N, int V, int MR, bool BFV, bool FUSE, int PB, int PF = 0>
+template <int N, int V, int MR, bool BFV, bool FUSE, int PB, int PF = 0, bool FULL = false>  // FULL: a fused level's staged_fp
 __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 && !BFV) ? RMC_FUSED_WAVES : 0) : (items_waves<N, V, MR, BFV>())) void k_expand_items(KParams P) {
+    static_assert(!FULL || FUSE, "only a fused level fingerprints here: a split chunk leaves it to k_hash_probe<..., FULL>");
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
     constexpr int NT = items_threads<N, V, MR, FUSE>();
@@ -2616,7 +2643,7 @@ __global__ __launch_bounds__((items_threads<N, V, MR, FUSE>()), FUSE ? ((N <= 3 
                         const ulonglong2 f = staged_fp<N, V, MR>(
                             P, sCore + j * NWP, [&](int pi) { return make_ulonglong2(m0[pi], m1[pi]); },
                             [&](int a, uint32_t) { return x.ainf[a]; }, st4[0], st4[1],
-                            S::SW4 > 2 ? st4[S::SW4 > 2 ? 2 : 0] : make_uint4(0u, 0u, 0u, 0u), sK);
+                            S::SW4 > 2 ? st4[S::SW4 > 2 ? 2 : 0] : make_uint4(0u, 0u, 0u, 0u), sK, FULL ? ~0u : 0u);
                         P.fp[q] = f;
                         P.lslot[q] = probe_elect<MX>(P, f, q, (x.nadd + (nmj & 1u) + 1u) >> 1, P.Lmask);
                     } else {
@@ -2764,7 +2791,7 @@ __device__ __forceinline__ uint32_t owner_bid(ESlot *OT, uint64_t mask, uint32_t
 #ifndef RMC_PROBE_WAVES  // waves per SIMD the probe pass's registers are cut for (0: the compiler's choice)
 #define RMC_PROBE_WAVES 0
 #endif
-template <int N, int V, int MR, int MX>
+template <int N, int V, int MR, int MX, bool FULL>  // FULL: rmc_set_full_state (staged_fp)
 __global__ __launch_bounds__(256, RMC_PROBE_WAVES) void k_hash_probe(KParams P) {
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
@@ -2823,7 +2850,7 @@ __global__ __launch_bounds__(256, RMC_PROBE_WAVES) void k_hash_probe(KParams P) 
         const ulonglong2 f = staged_fp<N, V, MR>(P, pc, [&](int pi) {
             const uint4 m = mp[pi];
             return make_ulonglong2((uint64_t)m.y << 32 | m.x, (uint64_t)m.w << 32 | m.z);
-        }, [&](int, uint32_t id) { return P.t.info[id]; }, sa, sb, sc, sK);
+        }, [&](int, uint32_t id) { return P.t.info[id]; }, sa, sb, sc, sK, FULL ? ~0u : 0u);
         const uint32_t nadd = sb.z >> 16;
         P.fp[sq] = f;
         if (P.route) {  // the owners probe and elect; the round's counts per owner (k_route_count's)
@@ -2910,7 +2937,7 @@ __global__ __launch_bounds__(256) void k_insert_winners(KParams P) {
 }
 
 // fingerprints of whole states (Init, test hooks): one wave per state
-template <int N, int V, int MR>
+template <int N, int V, int MR, bool FULL>
 __global__ __launch_bounds__(64) void k_fp_states(KParams P, uint64_t n) {
     using S = Spec<N, V, MR>;
     __shared__ uint64_t M0[N * N], M1[N * N];
@@ -2919,7 +2946,7 @@ __global__ __launch_bounds__(64) void k_fp_states(KParams P, uint64_t n) {
     for (uint64_t p = blockIdx.x; p < n; p += gridDim.x) {
         Wave<N, V, MR> W;
         load_parent<N, V, MR, true>(P, rec_start<S::RECW_MAX>(P, p), lane, W, M0, M1, pcore);
-        const ulonglong2 f = fingerprint<N, V>(W.c, M0, M1, P.t);
+        const ulonglong2 f = fingerprint<N, V>(W.c, M0, M1, P.t, FULL ? ~0u : 0u);
         if (lane == 0) P.fp[p] = f;
     }
 }
@@ -4201,7 +4228,7 @@ __device__ __forceinline__ unsigned long long gid_get(const GidMap &G, ulonglong
 }
 
 // n committed records into the map, a wave per record (k_fp_states' device code), record i as gid0 + i
-template <int N, int V, int MR>
+template <int N, int V, int MR, bool FULL>
 __global__ __launch_bounds__(64) void k_gid_insert(KParams P, uint64_t n, GidMap G, uint64_t gid0) {
     using S = Spec<N, V, MR>;
     __shared__ uint64_t M0[N * N], M1[N * N];
@@ -4210,7 +4237,7 @@ __global__ __launch_bounds__(64) void k_gid_insert(KParams P, uint64_t n, GidMap
     for (uint64_t p = blockIdx.x; p < n; p += gridDim.x) {
         Wave<N, V, MR> W;
         load_parent<N, V, MR, true>(P, rec_start<S::RECW_MAX>(P, p), lane, W, M0, M1, pcore);
-        const ulonglong2 f = fingerprint<N, V>(W.c, M0, M1, P.t);
+        const ulonglong2 f = fingerprint<N, V>(W.c, M0, M1, P.t, FULL ? ~0u : 0u);
         if (lane == 0) gid_put(G, f, gid0 + p);
         __syncthreads();  // the sums and the core in LDS are read out before the next record's go in
     }
@@ -4223,7 +4250,7 @@ __global__ __launch_bounds__(64) void k_gid_insert(KParams P, uint64_t n, GidMap
 // k_walk does) and fingerprinted as a whole state (k_fp_states' device code) unless it is its parent bit for
 // bit; then the lanes look the parent's fingerprints up in the gid map together -- one random 32-B read each
 // -- and write its edges, consecutive in the three output arrays, a lane per edge.  No global atomics.
-template <int N, int V, int MR, bool BFV>
+template <int N, int V, int MR, bool BFV, bool FULL>
 __global__ __launch_bounds__(64) void k_edges(KParams P, EdgeParams Ep) {
     using S = Spec<N, V, MR>;
     using Lo = Layout<N, V>;
@@ -4291,7 +4318,7 @@ __global__ __launch_bounds__(64) void k_edges(KParams P, EdgeParams Ep) {
             __syncthreads();
             Wave<N, V, MR> W2;
             load_parent<N, V, MR, true>(Pl, 0, lane, W2, M0, M1, qcore);
-            const ulonglong2 f = fingerprint<N, V>(W2.c, M0, M1, P.t);
+            const ulonglong2 f = fingerprint<N, V>(W2.c, M0, M1, P.t, FULL ? ~0u : 0u);
             if (lane == 0) sFp[idx] = f;
             __syncthreads();  // the record and the sums are read out before the next successor's go in
         }
@@ -4341,18 +4368,29 @@ struct Launch {
     static constexpr int MX = Spec<N, V, MR>::MAXS + (BFV ? Spec<N, V, MR>::MCAP : 0);
     static size_t bm_bytes(const KParams &P) { return (size_t)P.t.bmw * 4; }
     static void single(const KParams &P, hipStream_t s) {
-        hipLaunchKernelGGL((k_expand<N, V, MR, M_SINGLE, BFV>), dim3(1), dim3(64), bm_bytes(P), s, P);
+        // (every fingerprinting kernel is compiled per setting and picked here: the VIEW instantiations keep the
+        // registers and residency they had before rmc_set_full_state)
+        if (P.full) hipLaunchKernelGGL((k_expand<N, V, MR, M_SINGLE, BFV, true>), dim3(1), dim3(64), bm_bytes(P), s, P);
+        else hipLaunchKernelGGL((k_expand<N, V, MR, M_SINGLE, BFV, false>), dim3(1), dim3(64), bm_bytes(P), s, P);
     }
     static void fused(const KParams &P, hipStream_t s) {
         if (!P.route) {  // a block per XF_PARENTS parents, fingerprints and election in the same launch
             const uint64_t nbat = (P.p_end - P.p_begin + XF_PARENTS - 1) / XF_PARENTS;
-            hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, true, XF_PARENTS>), dim3(clamp_grid(nbat, 8192)),
-                               dim3(XB_THREADS), 0, s, P);
+            if (P.full)
+                hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, true, XF_PARENTS, 0, true>), dim3(clamp_grid(nbat, 8192)),
+                                   dim3(XB_THREADS), 0, s, P);
+            else
+                hipLaunchKernelGGL((k_expand_items<N, V, MR, BFV, true, XF_PARENTS, 0, false>), dim3(clamp_grid(nbat, 8192)),
+                                   dim3(XB_THREADS), 0, s, P);
             return;
         }
         // a sharded round below the split size: a wave per parent, fingerprints routed to their owners
-        hipLaunchKernelGGL((k_expand<N, V, MR, M_FUSED, BFV>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64),
-                           bm_bytes(P), s, P);
+        if (P.full)
+            hipLaunchKernelGGL((k_expand<N, V, MR, M_FUSED, BFV, true>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64),
+                               bm_bytes(P), s, P);
+        else
+            hipLaunchKernelGGL((k_expand<N, V, MR, M_FUSED, BFV, false>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64),
+                               bm_bytes(P), s, P);
     }
     // (grid: the blocks at most -- whole resident generations, which the engine sizes from items_blocks; 0: a
     // sharded round's fixed 2048.  The kernel's blocks stride over the batches, so each takes
@@ -4388,8 +4426,12 @@ struct Launch {
         Q.prun = P.route ? 1u : P.prun ? P.prun : (uint32_t)(fit < 1 ? 1 : fit < (uint64_t)PROBE_RUN ? fit : (uint64_t)PROBE_RUN);
         const uint64_t per = 256ull * Q.prun;
         const uint64_t blocks = (np + per - 1) / per;
-        hipLaunchKernelGGL((k_hash_probe<N, V, MR, MX>), dim3(clamp_grid(blocks, 16384)),
-                           dim3(256), 0, s, Q);
+        if (P.full)  // (the setting at compile time: the VIEW kernel keeps its registers and residency)
+            hipLaunchKernelGGL((k_hash_probe<N, V, MR, MX, true>), dim3(clamp_grid(blocks, 16384)),
+                               dim3(256), 0, s, Q);
+        else
+            hipLaunchKernelGGL((k_hash_probe<N, V, MR, MX, false>), dim3(clamp_grid(blocks, 16384)),
+                               dim3(256), 0, s, Q);
     }
     static void insert(const KParams &P, uint64_t np, hipStream_t s) {
         const uint64_t blocks = (np + 255) / 256;
@@ -4454,13 +4496,19 @@ struct Launch {
         if (n) hipLaunchKernelGGL((k_viol_scan<N, V, MR>), dim3(clamp_grid(b, 4096)), dim3(256), 0, s, P, n, vp);
     }
     static void gid_insert(const KParams &P, uint64_t n, GidMap g, uint64_t gid0, hipStream_t s) {
-        if (n) hipLaunchKernelGGL((k_gid_insert<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n, g, gid0);
+        if (!n) return;
+        if (P.full) hipLaunchKernelGGL((k_gid_insert<N, V, MR, true>), dim3(grid_for(n)), dim3(64), 0, s, P, n, g, gid0);
+        else hipLaunchKernelGGL((k_gid_insert<N, V, MR, false>), dim3(grid_for(n)), dim3(64), 0, s, P, n, g, gid0);
     }
     static void edges(const KParams &P, const EdgeParams &ep, hipStream_t s) {
-        hipLaunchKernelGGL((k_edges<N, V, MR, BFV>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64), bm_bytes(P), s, P, ep);
+        if (P.full)
+            hipLaunchKernelGGL((k_edges<N, V, MR, BFV, true>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64), bm_bytes(P), s, P, ep);
+        else
+            hipLaunchKernelGGL((k_edges<N, V, MR, BFV, false>), dim3(grid_for(P.p_end - P.p_begin)), dim3(64), bm_bytes(P), s, P, ep);
     }
     static void fps(const KParams &P, uint64_t n, hipStream_t s) {
-        hipLaunchKernelGGL((k_fp_states<N, V, MR>), dim3(grid_for(n)), dim3(64), 0, s, P, n);
+        if (P.full) hipLaunchKernelGGL((k_fp_states<N, V, MR, true>), dim3(grid_for(n)), dim3(64), 0, s, P, n);
+        else hipLaunchKernelGGL((k_fp_states<N, V, MR, false>), dim3(grid_for(n)), dim3(64), 0, s, P, n);
     }
     static void invs(const KParams &P, uint64_t n, int32_t *out, hipStream_t s) {
         hipLaunchKernelGGL((k_inv_states<N, V, MR>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, P, n, out);

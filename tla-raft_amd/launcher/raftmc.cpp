@@ -5,6 +5,7 @@
 //   raftmc -continue ... Raft.tla       (TLC's -continue: search past invariant violations, count them per invariant)
 //   raftmc -dump FILE | -dump dot[,actionlabels] FILE ... Raft.tla   (TLC's -dump: the state graph, FILE.dump / FILE.dot)
 //   raftmc -canreach NAME[=FALSE] ... Raft.tla   (GPU-specific: which states can still reach one where NAME holds)
+//   raftmc -fullstate ... Raft.tla      (GPU-specific: states are identified by all twelve variables, not the VIEW)
 //   raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config Raft.cfg] [-device D] [-msgcap C] Raft.tla
 //
 // Accepts the flags myrun.sh passes to TLC (myrun.sh:3), reads the same Raft.tla /
@@ -305,7 +306,7 @@ int usage(const char *msg) {
     std::fprintf(stderr, "raftmc: %s\nusage: raftmc [-deadlock] [-workers N] [-config FILE.cfg] [-device D] "
                          "[-gpus N [-onerank] [-shardmin K]] [-msgcap C] [-seenlog2 K] [-checkpoint MIN] [-metadir DIR] "
                          "[-recover DIR] [-coverage MIN] [-continue] [-dump [dot[,actionlabels]] FILE] [-canreach NAME[=FALSE]]... "
-                         "[-eventually NAME[=FALSE]]... [-leadsto Q[=FALSE] P[=FALSE]]... [-scc] FILE.tla\n"
+                         "[-fullstate] [-eventually NAME[=FALSE]]... [-leadsto Q[=FALSE] P[=FALSE]]... [-scc] FILE.tla\n"
                          "       raftmc -simulate [num=N] [-depth D] [-seed S] [-deadlock] [-config FILE.cfg] [-device D] "
                          "[-msgcap C] FILE.tla\n"
                          "  -coverage MIN  per-action coverage (distinct:generated) at the end of the search; the interval "
@@ -319,6 +320,9 @@ int usage(const char *msg) {
                          "still reach a state on which invariant NAME is TRUE (=FALSE: is FALSE), and the behaviour to the first "
                          "that cannot; NAME is one of Inv NoSplitVote RaftCanCommt FollowerCanCommit CommitAll NoAllCommit "
                          "ExistLeaderAndCandidate, in the cfg or not; one GPU, not with -simulate or -recover\n"
+                         "  -fullstate  (GPU-specific) identify states by all twelve variables instead of the cfg's VIEW, which "
+                         "leaves out electionCount, restartCount, pendingResponse and valSent; combines with every option "
+                         "of the search, not with -simulate (which keeps no set of states)\n"
                          "  -eventually NAME[=FALSE]  (GPU-specific, repeatable) after the search: from how many distinct states "
                          "every fair behaviour (a maximal path of the state graph) must reach a state on which NAME is TRUE "
                          "(=FALSE: is FALSE), how many can avoid it forever, and a counter-example if Init can; the fairness "
@@ -524,6 +528,7 @@ int main(int argc, char **argv) {
     long long sim_depth = 100;                           // TLC -depth
     bool coverage = false, cov_bad = false;              // TLC -coverage <minutes>
     bool cont = false;                                   // TLC -continue
+    bool fullstate = false;                              // -fullstate: the whole state, not the VIEW, is the identity
     bool dump = false, dump_dot = false, dump_labels = false;  // TLC -dump [dot[,options]] FILE
     std::string dump_file, dump_bad;
     std::vector<std::pair<int, int>> canreach;  // -canreach NAME[=FALSE]: (invariant bit, value)
@@ -579,6 +584,7 @@ int main(int argc, char **argv) {
             if (i + 1 >= argc || !isdigit((unsigned char)argv[i + 1][0])) cov_bad = true;
             else if (std::strtod(argv[++i], &end), *end) cov_bad = true;
         } else if (a == "-continue") cont = true;
+        else if (a == "-fullstate") fullstate = true;
         else if (a == "-dump") {
             dump = true;
             std::string v = need("-dump");
@@ -642,6 +648,8 @@ int main(int argc, char **argv) {
         if (simulate) return usage("-coverage cannot be combined with -simulate");
         if (!recover_dir.empty()) return usage("-coverage cannot be combined with -recover (checkpoints do not carry it)");
     }
+    if (fullstate && simulate)  // refused before anything touches a device
+        return usage("-fullstate cannot be combined with -simulate (random walks keep no set of states)");
     if (cont) {  // refused before anything touches a device
         if (simulate) return usage("-continue cannot be combined with -simulate");
         if (!recover_dir.empty()) return usage("-continue cannot be combined with -recover (checkpoints do not carry the violation counts)");
@@ -733,6 +741,7 @@ int main(int argc, char **argv) {
     std::printf("Semantic processing of module %s\n", pm.module.c_str());
     for (const auto &c : pm.ignored_constants) std::printf("(ignoring assignment to undeclared constant %s)\n", c.c_str());
     std::printf("Starting... (%s)\n", now_str().c_str());
+    if (fullstate) std::printf("Fingerprinting the whole state: the cfg's VIEW view is not applied.\n");
     // TLC's error lines and "The behavior up to this point is:" block for the context's trace; returns
     // TLC's exit code for the status
     // the name the cfg used for an invariant (Inv and LeaderHasAllCommittedEntries share bit 0)
@@ -861,6 +870,11 @@ int main(int argc, char **argv) {
     phase_time("created");
     if (rc != RMC_OK) { std::printf("Error: could not start the GPU model checker (code %d): %s\n", rc, rmc_last_error(nullptr)); return 75; }
     rmc_level_stats st;
+    if (fullstate && rmc_set_full_state(ctx, 1) < 0) {
+        std::printf("Error: %s\n", rmc_last_error(ctx));
+        rmc_destroy(ctx);
+        return 75;
+    }
     if (coverage && rmc_set_coverage(ctx, 1) < 0) {
         std::printf("Error: %s\n", rmc_last_error(ctx));
         rmc_destroy(ctx);

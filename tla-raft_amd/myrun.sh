@@ -8,5 +8,7 @@
 #   -eventually NAME[=FALSE] | -leadsto Q[=FALSE] P[=FALSE]   (repeatable) from how many states NAME must follow on every
 #   fair behaviour, how many can avoid it forever, and a counter-example (a lasso or a dead end) when the property fails
 #   -scc   the strongly connected components of the state graph
+#   -fullstate   identify states by all twelve variables instead of the cfg's VIEW (which leaves out electionCount,
+#   restartCount, pendingResponse and valSent); one extra line after the header, the counters are then of whole states
 DIR=$(cd "$(dirname "$0")" && pwd)
 "$DIR/build/raftmc" -deadlock -workers 4 -config Raft.cfg Raft.tla $@ 2>&1 | tee raft.log

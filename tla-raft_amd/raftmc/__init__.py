@@ -216,6 +216,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "rmc_set_coverage"):
         lib.rmc_set_coverage.argtypes = [vp, i32]
         lib.rmc_get_coverage.argtypes = [vp, P(_Coverage)]
+    if hasattr(lib, "rmc_set_full_state"):  # (likewise)
+        lib.rmc_set_full_state.argtypes = [vp, i32]
     if hasattr(lib, "rmc_set_continue"):  # (likewise)
         lib.rmc_set_continue.argtypes = [vp, i32]
         lib.rmc_get_violations.argtypes = [vp, P(_Violations)]
@@ -253,6 +255,7 @@ class ModelConfig:
     check_deadlock: bool = False
     spec_variant: int = SPEC_RAFT
     symmetry: bool = True
+    view: bool = True                # False: states are identified by all twelve variables (set_full_state)
     device: int = -1
     msg_cap: int = 0
     seen_log2: int = 0
@@ -688,6 +691,12 @@ class ModelChecker:
         self.h = h
         self.levels: List[LevelStats] = []
         self._inited = False
+        if not cfg.view:
+            try:
+                self.set_full_state(True)
+            except RmcError:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -837,6 +846,15 @@ class ModelChecker:
             out.keys = [[(k >> 24, (k >> 16) & 0xFF, k & 0xFFFF) for k in keys[w * d1:w * d1 + max(n - 1, 0)]]
                         for w, n in enumerate(out.lengths)]
         return out
+
+    def set_full_state(self, on: bool = True) -> None:
+        """Identify states by all twelve variables instead of the cfg's VIEW (include/rmc.h
+        rmc_set_full_state): the seen set, coverage, continuation, graph mode, fingerprint(s) and
+        seen_contains then work on whole states.  On a fresh or reset checker, before init() / run();
+        reset() keeps it.  ModelConfig(view=False) calls this right after create."""
+        if not hasattr(self.lib, "rmc_set_full_state"):
+            raise RmcError("this librmc.so cannot search on the whole state (rmc_set_full_state): rebuild it")
+        self._check(self.lib.rmc_set_full_state(self.h, 1 if on else 0))
 
     def set_coverage(self, on: bool = True) -> None:
         """TLC's -coverage: count, per action of Next, the successors generated and the states first found
@@ -1145,6 +1163,17 @@ class ModelChecker:
                           ctypes.POINTER(ctypes.c_int32))
         self._check(self.lib.rmc_fingerprints(self.h, buf, stride, n, fps))
         return [(fps[2 * i], fps[2 * i + 1]) for i in range(n)]
+
+    def fingerprints_array(self, unpacked):
+        """fingerprints_unpacked for a C-contiguous int32 numpy array of shape (n, stride), as a (n, 2) uint64
+        array (no Python object per state: millions of states a call)."""
+        import numpy as np
+        n, stride = unpacked.shape
+        assert unpacked.dtype == np.int32 and unpacked.flags["C_CONTIGUOUS"]
+        fps = np.empty((max(n, 1), 2), dtype=np.uint64)
+        self._check(self.lib.rmc_fingerprints(self.h, unpacked.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), stride, n,
+                                              fps.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return fps[:n]
 
     def seen_contains(self, fps: Sequence[Tuple[int, int]]) -> List[bool]:
         """Membership of each fingerprint in the seen set (TLC's FPSet)."""
